@@ -14,7 +14,11 @@ The batch is in STEADY STATE: the B requests start at generated positions spread
 requests finish (and are replaced by fresh ones, prompt-tree build included) inside the timed region at the
 rate a long run would see, contexts average prompt + gen/2, and the response trees are populated.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what is measured after the timed
+region: the other proposal-indexing mode, the LSTM-only leg (BASELINE configs[1]), the extra all-to-all steps of N > 1,
+the golden suffix replay check and the CPU baseline.  --dump-outputs DIR writes what the last timed step computed
+(accepted tokens, next drafts, attention output) as DIR/<name>.npy.
 N > 1: Ulysses sequence parallelism over the N ranks (heads sharded, all-to-all around attention over RCCL,
 vocab-parallel draft LM head); the global batch is fixed, so scaling is "strong".  Launched by
 torch.distributed.run (WORLD_SIZE set) the process is one rank; started plainly with --gpus N > 1 it starts
@@ -52,6 +56,13 @@ def parse_args():
     ap.add_argument("--prompt-len", type=int, default=4096)
     ap.add_argument("--gen-len", type=int, default=256)
     ap.add_argument("--layers", type=int, default=32)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what is measured beside the headline, after the timed region: the other proposal-indexing "
+                         "mode, the LSTM-only leg, the extra all-to-all steps (N > 1), the golden suffix replay check and the "
+                         "CPU baseline (each can still be skipped with its --no-* switch)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64): "
+                         "tokens accepted per request, the drafts proposed for the next step, the attention output")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-attn-graph", action="store_true",
                     help="launch the attention layers kernel by kernel instead of as one HIP graph per step (A/B switch)")
@@ -70,14 +81,14 @@ def parse_args():
                          "algorithm of the reference's simulator and of the golden fixtures) — the headline is what the plugin "
                          "does out of the box.  \"reference\" is the opt-in switch for the reference plugin's literal arithmetic "
                          "(sampled ids counted twice, model_runner.py:623-636 / :696-718).  The other mode's acceptance is "
-                         "measured in a few extra rounds after the timed region and printed beside the headline")
+                         "measured in a few extra rounds after the timed region and printed beside the headline (--full)")
     ap.add_argument("--plant-draft-prob", type=float, default=0.7,
-                    help="draft-model legs only (--no-suffix, and the LSTM-only leg of the default run): probability, per draft "
+                    help="draft-model legs only (--no-suffix, and the LSTM-only leg of a --full run): probability, per draft "
                          "position, that the synthetic target's arg-max token IS the draft model's token (SURVEY 8(d): \"the "
                          "draft token planted as argmax with prob 0.7 per position\"); a random-weight draft model never hits "
                          "the ground-truth stream, so without it that leg's acceptance is identically 0")
     ap.add_argument("--no-lstm-leg", action="store_true",
-                    help="skip the LSTM-only leg (BASELINE configs[1]) that the default run measures after the timed region")
+                    help="skip the LSTM-only leg (BASELINE configs[1]) that --full measures after the timed region")
     ap.add_argument("--no-replay-check", action="store_true",
                     help="skip the one-request-at-a-time suffix replay on the golden token source (method \"suffix\", every "
                          "draft taken; its avg_accept_toks must equal tests/golden/suffix_replay.json)")
@@ -299,6 +310,30 @@ def suffix_replay_check():
                     "device suffix cache just now; golden = the compiled reference's run (tests/golden/suffix_replay.json)"}
 
 
+DUMP_BUDGET_BYTES = 48 << 20      # --dump-outputs: at most this much in all (a larger array is row-sampled, seeded)
+
+
+def write_outputs(out_dir: str, arrays: dict) -> None:
+    """--dump-outputs: every array as out_dir/<name>.npy.  Integer arrays (token ids, counts) are written as float64, which
+    holds them exactly; floating-point ones as float32.  An array larger than what is left of DUMP_BUDGET_BYTES keeps a fixed,
+    seeded sample of its rows (in order), and the indices of those rows go beside it as <name>_rows.npy.  The smallest
+    arrays are written first, so that only the largest can need sampling."""
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for name, a in sorted(arrays.items(), key=lambda kv: np.asarray(kv[1]).size):
+        a = np.asarray(a)
+        a = a.astype(np.float64) if a.dtype.kind in "iub" else a.astype(np.float32)
+        row_bytes = max(a[0].nbytes if a.ndim and len(a) else a.nbytes, 1)
+        if a.nbytes > left and a.ndim:
+            keep = max(min(len(a), left // row_bytes - 1), 0)
+            rows = np.sort(np.random.default_rng(0).choice(len(a), size=keep, replace=False))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            left -= rows.nbytes
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+
+
 def spawn_ranks(args) -> int:
     """`bench.py --gpus N` without a launcher: start N ranks as a CHILD process tree (never an exec: this process has
     not touched the GPU, and must not before the children exist) and hand back their exit code."""
@@ -345,7 +380,7 @@ def main():
         assert dist.get_world_size() == world   # n_gpus below is the size of the group that really formed
 
     from arcticinference_amd import _native as N
-    from arcticinference_amd.engine import HotPathEngine, ModelShape, SpecConfig
+    from arcticinference_amd.engine import MAX_SPEC_LEN, HotPathEngine, ModelShape, SpecConfig
     from arcticinference_amd.speculator import ArcticLSTMSpeculator, LSTMSpeculatorConfig, random_lstm_weights
     from arcticinference_amd.workload import TokenSource
 
@@ -385,7 +420,7 @@ def main():
                                        quantize_lm_head=True)
         lstm_ckpt = random_lstm_weights(cfg, seed=args.seed)
         drafter.load_weights(lstm_ckpt.items())
-        if rank != 0 or world > 1 or args.no_cpu_baseline:
+        if rank != 0 or world > 1 or args.no_cpu_baseline or not args.full:
             lstm_ckpt = None            # rank 0 of a single-GPU run keeps the host copy for the cpu_baseline leg
         draft_cfg = cfg
         drafter = TimedDrafter(drafter)
@@ -520,10 +555,39 @@ def main():
     steps_sp = ulysses.steps_sp if ulysses is not None else 0
     draft_timing = drafter.summary(draft_cfg, spec.num_speculative_tokens) if drafter is not None else None
 
+    # --dump-outputs: what the last timed round computed.  Its lane steps were begun and have run on the device; their host
+    # halves are finished here (lane by lane, as the next round would), which gives what a caller receives from the step:
+    # the tokens accepted per request and the drafts proposed for its next step.  The attention output buffer holds the
+    # last layer of the round's last lane step.
+    if args.dump_outputs:
+        dump = {}
+        last = pending[n_lanes - 1]
+        if ulysses is None and last is not None:
+            t_last = int((last.n_draft + 1).sum())
+            dump["attention_out"] = eng.attn_out[:t_last].float().cpu().numpy()
+        accepted = np.full((B, MAX_SPEC_LEN + 1), -1, dtype=np.int64)
+        drafts = np.full((B, MAX_SPEC_LEN), -1, dtype=np.int64)
+        for l in range(n_lanes):
+            c, pending[l] = pending[l], None
+            if c is None:
+                continue
+            emitted = eng.finish(c)
+            for i, slot in enumerate(c.live.tolist()):
+                accepted[slot, :emitted.counts[i]] = emitted[i]
+                d = eng.requests[slot].drafts
+                drafts[slot, :len(d)] = d
+            account(c.live, emitted)
+        dump["accepted_tokens"] = accepted
+        dump["accepted_counts"] = (accepted >= 0).sum(axis=1)
+        dump["next_draft_tokens"] = drafts
+        dump["next_draft_counts"] = (drafts >= 0).sum(axis=1)
+        if rank == 0:
+            write_outputs(args.dump_outputs, dump)
+
     # the OTHER reading of the proposal indexing, a few rounds on the same engine outside `value` (every rank runs them:
     # the control flow is replicated): its acceptance and step time go into the line beside the headline mode's
     other_mode = None
-    if eng.suffix_cache is not None and not args.no_spec:
+    if args.full and eng.suffix_cache is not None and not args.no_spec:
         from arcticinference_amd.vllm_plugin.runner_logic import INDEXING_MODES
         other = [m for m in INDEXING_MODES if m != eng._indexing][0]
         headline_mode, eng._indexing = eng._indexing, other
@@ -553,7 +617,7 @@ def main():
     # N > 1 with shift parallelism: the decode-size steps above ran in shift (TP) mode.  A few extra steps, outside
     # `value`, with shift off put the Ulysses all-to-all path (2 RCCL all_to_all_single per layer) on the record too.
     a2a_ms, a2a_error = None, None
-    if ulysses is not None and ulysses.enable_shift_parallel and steps_shift > 0:
+    if args.full and ulysses is not None and ulysses.enable_shift_parallel and steps_shift > 0:
         # an error here (the same on every rank: the inputs are seeded alike) must not cost the run its JSON line
         try:
             ulysses.enable_shift_parallel = False
@@ -581,7 +645,7 @@ def main():
     # agrees with each draft token with probability --plant-draft-prob per position, so tokens/s, accepted
     # length and the draft model's roofline entry (every call bracketed by an event pair) are real numbers.  One GPU only.
     lstm_leg = None
-    if (world == 1 and drafter is not None and eng.suffix_cache is not None and not args.no_spec and not args.no_suffix
+    if (args.full and world == 1 and drafter is not None and eng.suffix_cache is not None and not args.no_spec and not args.no_suffix
             and not args.no_lstm_leg):
         eng.suffix_cache = None                     # nothing below uses it again (the replay check builds its own)
         eng.spec.enable_suffix_decoding = False
@@ -644,20 +708,21 @@ def main():
                 except Exception:
                     traffic = None
         replay_check = None
-        if world == 1 and not args.no_replay_check and not args.no_spec:
+        if args.full and world == 1 and not args.no_replay_check and not args.no_spec:
             try:
                 replay_check = suffix_replay_check()
             except Exception as e:                      # noqa: BLE001 - reported, not swallowed
                 replay_check = {"error": "%s: %s" % (type(e).__name__, e)}
         golden_accept = None
-        try:
-            with open(os.path.join(ROOT, "tests", "golden", "suffix_replay.json")) as f:
-                gr = json.load(f)[-1]
-            golden_accept = {"avg_accept_toks": gr["avg_accept_toks"], "sum_accept": gr["sum_accept"], "steps": gr["steps"],
-                             "what": "the compiled reference's suffix proposer alone (method \"suffix\": every draft taken), "
-                                     "one request at a time, same token source: tests/golden/suffix_replay.json"}
-        except Exception:
-            pass
+        if args.full:
+            try:
+                with open(os.path.join(ROOT, "tests", "golden", "suffix_replay.json")) as f:
+                    gr = json.load(f)[-1]
+                golden_accept = {"avg_accept_toks": gr["avg_accept_toks"], "sum_accept": gr["sum_accept"], "steps": gr["steps"],
+                                 "what": "the compiled reference's suffix proposer alone (method \"suffix\": every draft taken), "
+                                         "one request at a time, same token source: tests/golden/suffix_replay.json"}
+            except Exception:
+                pass
         line = {
             "metric": "gen tokens/sec/GPU + mean accepted draft len, Llama-3.1-8B spec-decode SP=1/8",
             "value": value,
@@ -671,6 +736,7 @@ def main():
             "vs_baseline": None,
             "dtype": "bf16",
             "data": "synthetic",
+            "full": args.full,
             "config": {
                 "workload": ("Llama-3.1-8B shapes (L=%d, Hq=32, Hkv=8, D=128, V=128256), %sB=%d live requests, "
                              "%d-token prompts, %d generated tokens each, greedy, KV cache %s; hot path only (verify "
@@ -770,7 +836,7 @@ def main():
         if cands:
             best = max(cands, key=lambda c: c[0]["calls"])
             line["roofline_draft_model"] = draft_roofline(*best)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             toks_per_req_step = st.emitted / max(args.steps * B, 1)
             cb = cpu_baseline(args, src, shape, spec, {"steps": st.steps, "draft_model_steps": st.draft_model_steps,
                                                        "replacements_per_step": replaced_total / max(args.steps, 1),

@@ -106,7 +106,7 @@ def test_bench_runs_through_a_one_rank_rccl_group(extra):
     env = dict(os.environ, AIC_BENCH_ONE_RANK_GROUP="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "8", "--prompt-len", "512",
-           "--gen-len", "64", "--layers", "4", "--no-cpu-baseline", "--no-replay-check"] + extra
+           "--gen-len", "64", "--layers", "4", "--full", "--no-cpu-baseline", "--no-replay-check"] + extra
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

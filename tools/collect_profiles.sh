@@ -21,17 +21,17 @@ if [ "$STAGE" = tests ]; then
 fi
 
 if [ "$STAGE" = bench ]; then
-  timeout -k 10 600 python bench.py 2> $O/bench.err | grep '^{' > $O/bench.json
+  timeout -k 10 600 python bench.py --full 2> $O/bench.err | grep '^{' > $O/bench.json
   cut -c1-300 $O/bench.json
-  timeout -k 10 300 python bench.py --lanes 1 $Q 2>> $O/bench.err | grep '^{' > $O/bench_1lane.json
-  timeout -k 10 300 python bench.py --steps 20 --warmup 5 2>> $O/bench.err | grep '^{' > $O/bench_20steps.json
-  timeout -k 10 300 python bench.py --kv-dtype fp8 $Q 2>> $O/bench.err | grep '^{' > $O/bench_fp8kv.json
+  timeout -k 10 300 python bench.py --full --lanes 1 $Q 2>> $O/bench.err | grep '^{' > $O/bench_1lane.json
+  timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 2>> $O/bench.err | grep '^{' > $O/bench_20steps.json
+  timeout -k 10 300 python bench.py --full --kv-dtype fp8 $Q 2>> $O/bench.err | grep '^{' > $O/bench_fp8kv.json
   # speculation against plain decode on the same engine, same box, one after the other (the stand-in for the north star's
   # ">= 2x vanilla": vLLM is on neither box): configs[1] (LSTM alone, drafts planted at p = 0.7), default, speculation off
   timeout -k 10 300 python bench.py --no-suffix --no-cpu-baseline --no-replay-check 2>> $O/bench.err | grep '^{' > $O/bench_nosuffix.json
   timeout -k 10 300 python bench.py --no-spec --no-cpu-baseline --no-replay-check 2>> $O/bench.err | grep '^{' > $O/bench_nospec.json
   timeout -k 10 300 python bench.py --no-spec --lanes 1 --no-cpu-baseline --no-replay-check 2>> $O/bench.err | grep '^{' > $O/bench_nospec_1lane.json
-  timeout -k 10 300 python bench.py --proposal-indexing reference $Q 2>> $O/bench.err | grep '^{' > $O/bench_reference_indexing.json
+  timeout -k 10 300 python bench.py --full --proposal-indexing reference $Q 2>> $O/bench.err | grep '^{' > $O/bench_reference_indexing.json
   python - <<'EOF' > $O/bench_spec_vs_nospec.txt
 import json, os
 O = os.path.join(os.environ.get("GRAFT_REPO_ROOT", os.getcwd()), "gpurun_out", "art")
@@ -74,14 +74,14 @@ fi
 
 if [ "$STAGE" = profile ]; then
   cd /tmp && export TMPDIR=/tmp
-  rocprofv3 --kernel-trace --stats --output-format csv rocpd -d $O/stats -o p -- python3 $R/bench.py $Q > $O/stats.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv rocpd -d $O/stats -o p -- python3 $R/bench.py --full $Q > $O/stats.log 2>&1
   echo stats done
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_nosuffix -o p -- python3 $R/bench.py --no-suffix --no-cpu-baseline --no-replay-check > $O/stats_nosuffix.log 2>&1
   echo nosuffix stats done
-  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o p -- python3 $R/bench.py --steps 4 --warmup 2 $Q > $O/pmc_fetch.log 2>&1
+  rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o p -- python3 $R/bench.py --full --steps 4 --warmup 2 $Q > $O/pmc_fetch.log 2>&1
   grep '^{' $O/pmc_fetch.log > $O/pmc_bench.json || true
   echo fetch pass done
-  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o p -- python3 $R/bench.py --steps 4 --warmup 2 $Q > $O/pmc_write.log 2>&1
+  rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o p -- python3 $R/bench.py --full --steps 4 --warmup 2 $Q > $O/pmc_write.log 2>&1
   echo write pass done
   cd $R
   DB=$(find $O/stats -name '*.db' | head -1)

@@ -10,7 +10,7 @@ run() {
   n=$1; shift
   echo "== $n ranks: $*"
   timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29500 + n)) \
-    bench.py --gpus $n --dist-backend gloo --steps 6 --warmup 2 --no-cpu-baseline --no-replay-check "$@" 2> gpurun_out/rehearse_gloo_$n.err | grep '^{' | python -c "
+    bench.py --gpus $n --dist-backend gloo --steps 6 --warmup 2 --full --no-cpu-baseline --no-replay-check "$@" 2> "${TMPDIR:-/tmp}/rehearse_gloo_$n.err" | grep '^{' | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print(d['n_gpus'], round(d['value']), round(d['ms_per_step'],2), d['config']['parallelism'], 'shift', d['steps_in_shift_mode'], 'sp', d['steps_in_sp_mode'],

@@ -7,7 +7,7 @@ SP=$1; L=$2; shift 2
 O=$R/gpurun_out/spt_${SP}_${L}
 rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format rocpd -d $O -o p -- python3 $R/bench.py --rehearse-sp $SP --lanes $L --no-cpu-baseline "$@" > $O/log 2>&1
+rocprofv3 --kernel-trace --output-format rocpd -d $O -o p -- python3 $R/bench.py --full --rehearse-sp $SP --lanes $L --no-cpu-baseline "$@" > $O/log 2>&1
 cd $R
 grep '^{' $O/log | cut -c1-200
 DB=$(find $O -name '*.db' | head -1)
