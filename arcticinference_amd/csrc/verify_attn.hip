@@ -36,19 +36,12 @@
 #include <cstdlib>
 
 #include "aic_common.h"
+#include "attn_common.h"
 
 namespace aic {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
 
-// The block table is read-only for the kernels: addressed through the constant address space with wave-uniform
-// indices its lookups become scalar loads (s_load_dword, lgkmcnt) and stay out of the vector-memory queue, where
-// a dependent lookup between data loads would force the in-order vmcnt to drain every load issued before it.
-typedef const int32_t __attribute__((address_space(4)))* const_i32_ptr;
 
-constexpr int kTile = 32;  // tokens per inner step
 constexpr int kD = 128;
 
 struct AttnParams {
@@ -110,23 +103,7 @@ __device__ __forceinline__ int window_begin(const AttnParams& P, int ctx, int q_
   return lo > 0 ? (lo & ~(kTile - 1)) : 0;
 }
 
-// 16-byte load of KV bytes, non-temporal: every byte of the cache is read once per call, and with the default
-// policy the stream evicts itself through the L2 (measured on the B = 64 x 4096-token case: 190.7 -> 171.0 us per
-// call, 5.63 -> 6.28 TB/s).
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
-__device__ __forceinline__ uint4 ld_kv16(const char* p) {
-  const u32x4_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p));
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
 
-// Byte offset of 16-byte chunk `ch` (0..15) of token `t` (0..31) in the wave's V tile.  256-byte rows with
-// the chunk index XOR-ed by a function of the row (cdna guide T10, image (b)), and token groups 4-7 /
-// 8-11 swapped between rows so that the two 4-row blocks a 32-lane half reads transposed sit 8 rows
-// apart: both the ds_write_b128 fill and the ds_read_b64_tr_b16 reads are then bank-conflict free.
-__device__ __forceinline__ int v_tile_off(int t, int ch) {
-  const int row = (t & ~12) | ((t & 4) << 1) | ((t & 8) >> 1);
-  return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-}
 
 // WH (waves = heads): the four waves of a workgroup take four consecutive kv heads over the SAME token
 // range, so the workgroup reads 4 x 256 B = 1 KiB contiguous per token and the heads of a token are
@@ -145,15 +122,6 @@ __device__ __forceinline__ int tile_off(int t, int ch) {
   }
 }
 
-// Lanes c16 + 16 g (g = 0..3) hold the same query row.  gfx950's row / half swaps combine them on the VALU
-// (ds_bpermute costs an LDS round trip per step, and the long-draft kernel is VALU/latency bound).  The
-// s_nops are the VALU-write -> permlane-swap -> VALU-read hazards the assembler does not see inside asm.
-__device__ __forceinline__ void swap16(float& a, float& b) {
-  asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 0" : "+v"(a), "+v"(b));
-}
-__device__ __forceinline__ void swap32(float& a, float& b) {
-  asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1\n\ts_nop 0" : "+v"(a), "+v"(b));
-}
 // maxima without the canonicalising v_max(x, x) the compiler puts in front of every fmaxf of a value it cannot prove quiet
 // (MFMA results): scores are never signalling NaNs
 __device__ __forceinline__ float max3f(float a, float b, float c) {
@@ -169,22 +137,6 @@ __device__ __forceinline__ float max_nc(float a, float b) {
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr float kLazySlack = 6.0f;   // long-draft body: a row's adopted maximum may trail the true one by this much (base-2 exponent)
 
-__device__ __forceinline__ float rowgroup_max(float x) {
-  float a = x, b = x;
-  swap16(a, b);
-  a = a > b ? a : b;
-  b = a;
-  swap32(a, b);
-  return a > b ? a : b;
-}
-__device__ __forceinline__ float rowgroup_sum(float x) {
-  float a = x, b = x;
-  swap16(a, b);
-  a += b;
-  b = a;
-  swap32(a, b);
-  return a + b;
-}
 
 // Online-softmax update of one 16-row query tile against one 32-token KV tile, in the S^T layout: the lane owns
 // query row c16 and the 8 tokens tt + 16 th + 4 g + e.  Scores stay raw; the scale (folded with log2 e, v_exp_f32 is base 2)
@@ -243,20 +195,6 @@ __device__ __forceinline__ void softmax_tile(const f32x4& s0, const f32x4& s1, b
   }
 }
 
-// 8 e4m3 bytes (two dwords) -> 8 bf16 (exact: every e4m3 value is a bf16 value).  gfx950's scaled converts take two
-// fp8 to two bf16 in ONE instruction (v_cvt_scalef32_pk_bf16_fp8, scale 1.0): 4 VALU per 8 elements where the
-// fp8 -> f32 -> bf16 route took 8.  SQ counters on the fp8 short body (profiles/r02_pmc_secondary_kernels.txt): 70.8 % of
-// its wave cycles were instruction issue (bf16 body: 32 %), 1.15e8 VALU instructions for half the bytes of the bf16
-// body's 8.3e7 — the conversion made it issue-bound.
-__device__ __forceinline__ bf16x8 fp8x8_to_bf16x8(uint32_t lo, uint32_t hi) {
-  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-  const bf16x2_t a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(static_cast<int>(lo), 1.0f, false);
-  const bf16x2_t b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(static_cast<int>(lo), 1.0f, true);
-  const bf16x2_t c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(static_cast<int>(hi), 1.0f, false);
-  const bf16x2_t d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(static_cast<int>(hi), 1.0f, true);
-  return __builtin_shufflevector(__builtin_shufflevector(a, b, 0, 1, 2, 3), __builtin_shufflevector(c, d, 0, 1, 2, 3), 0, 1,
-                                 2, 3, 4, 5, 6, 7);
-}
 
 // Rows written by a launch with fewer splits than the call's slot count end their slot list with a sentinel
 // {-inf, -2} in the first unused slot: the combine kernel stops there.  (Marking every unused slot empty — 14 scattered
@@ -270,8 +208,6 @@ __device__ __forceinline__ void mark_unused_parts(const AttnParams& P, int64_t g
   }
 }
 
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kLn2 = 0.6931471805599453f;
 
 // KV8: the cache holds OCP e4m3 bytes (A16 writes them); tiles are dequantised to bf16 in registers (exact),
 // k_scale folds into the soft-max scale and v_scale into the output, so no per-element scaling is needed.

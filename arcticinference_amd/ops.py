@@ -287,6 +287,96 @@ def split_requests(q_lens_host: Sequence[int], group_size: int, device, order_de
 
 
 # ------------------------------------------------------------------------------------------------
+# A5p whole-step attention: decodes, long drafts and prefill chunks in one call
+# ------------------------------------------------------------------------------------------------
+MAX_DECODE_Q_LEN = 33     # MAX_SPEC_LEN + 1: longer queries are prefill chunks (aic_step_attention's prefill body)
+
+
+def split_order3(q_lens_host: Sequence[int], group_size: int):
+    """Three-way partition of a step for aic_step_attention: (request ids as int32 = the short requests, then the
+    prefill requests, then the long drafts, each in batch order; n_short, n_prefill, n_long).  Prefill = q_len >
+    MAX_DECODE_Q_LEN; short = q_len * Hq/Hkv <= 32 query rows (split_order's rule); long = the rest."""
+    import numpy as np
+    ql = np.asarray(q_lens_host, dtype=np.int64)
+    is_pf = ql > MAX_DECODE_Q_LEN
+    is_short = ~is_pf & (ql * group_size <= 32)
+    is_long = ~is_pf & ~is_short
+    order = np.concatenate([np.nonzero(is_short)[0], np.nonzero(is_pf)[0], np.nonzero(is_long)[0]]).astype(np.int32)
+    return order, int(is_short.sum()), int(is_pf.sum()), int(is_long.sum())
+
+
+def decode_index(q_lens_host: Sequence[int]):
+    """Compact layout of a step's decode rows: (query_start_loc int32 [B + 1] in which every prefill request has an empty
+    range, token of the call of each compact row int32 [num_decode_tokens], max decode q_len)."""
+    import numpy as np
+    ql = np.asarray(q_lens_host, dtype=np.int64)
+    dec = np.where(ql > MAX_DECODE_Q_LEN, 0, ql)
+    qsl = np.zeros(len(ql) + 1, dtype=np.int32)
+    np.cumsum(dec, out=qsl[1:])
+    starts = np.zeros(len(ql), dtype=np.int64)
+    np.cumsum(ql[:-1], out=starts[1:])
+    idx = np.concatenate([np.arange(s, s + n, dtype=np.int32) for s, n in zip(starts, dec) if n > 0]) \
+        if dec.sum() > 0 else np.zeros(0, dtype=np.int32)
+    return qsl, idx.astype(np.int32), int(dec.max()) if len(dec) else 0
+
+
+class StepSplit:
+    """What aic_step_attention needs of a step's per-request query lengths, built once per step (host + one upload)
+    and shared by every layer: the three-way request lists and the compact decode layout."""
+
+    def __init__(self, q_lens_host: Sequence[int], group_size: int, device):
+        import numpy as np
+        ql = np.asarray(q_lens_host, dtype=np.int64)
+        order, self.n_short, self.n_prefill, self.n_long = split_order3(ql, group_size)
+        qsl, idx, self.max_decode_q_len = decode_index(ql)
+        self.num_decode_tokens = int(idx.size)
+        self.max_prefill_q_len = int(ql[ql > MAX_DECODE_Q_LEN].max()) if self.n_prefill else 0
+        self.num_tokens = int(ql.sum())
+        self.batch = int(ql.size)
+        staged = torch.from_numpy(np.concatenate([order, qsl, idx]).astype(np.int32)).to(device, non_blocking=True)
+        B = self.batch
+        self.req_lists = staged[:B]
+        self.decode_qsl = staged[B:2 * B + 1]
+        self.decode_index = staged[2 * B + 1:]
+
+
+def step_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor,
+                   seq_lens: torch.Tensor, query_start_loc: torch.Tensor, max_seq_len: int, sm_scale: float,
+                   q_lens_host: Optional[Sequence[int]] = None, step_split: Optional[StepSplit] = None,
+                   out: Optional[torch.Tensor] = None, num_splits_max: int = 64,
+                   k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None,
+                   stream: Optional[int] = None) -> torch.Tensor:
+    """Attention for a whole step whatever its query lengths (aic_step_attention): prefill chunks (q_len > 33) beside
+    decodes and long drafts, in any batch order.  Same tensors and conventions as verify_attention; the step's
+    geometry comes from `q_lens_host` or a StepSplit built from it once per step (pass that to every layer)."""
+    _need_cuda(q, k_cache, v_cache, block_table, seq_lens, query_start_loc)
+    T, Hq, D = q.shape
+    nb, bs, Hkv, D2 = k_cache.shape
+    assert D == D2 and q.stride(2) == 1 and q.stride(1) == D
+    if step_split is None:
+        if q_lens_host is None:
+            raise ValueError("step_attention needs the step's per-request query lengths (q_lens_host or step_split)")
+        step_split = StepSplit(q_lens_host, Hq // Hkv, q.device)
+    sp = step_split
+    if sp.batch != seq_lens.numel() or sp.num_tokens > T:
+        raise ValueError("the step split does not describe this call")
+    if out is None:
+        out = torch.empty((T, Hq, D), dtype=q.dtype, device=q.device)
+    wsb = N.lib().aic_step_attention_workspace_bytes(sp.num_decode_tokens, sp.n_prefill, sp.max_prefill_q_len, Hq, Hkv, D,
+                                                     num_splits_max)
+    ws = _workspace(wsb, q.device, stream)
+    N.check(N.lib().aic_step_attention(
+        q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(0),
+        N.torch_dtype_code(k_cache.dtype), _ptr(k_scale), _ptr(v_scale), block_table.data_ptr(), block_table.size(1),
+        seq_lens.data_ptr(), query_start_loc.data_ptr(), sp.batch, sp.num_tokens, Hq, Hkv, D, bs, float(sm_scale),
+        out.data_ptr(), out.stride(0), ws.data_ptr(), ws.numel(), int(max_seq_len), sp.req_lists.data_ptr(), sp.n_short,
+        sp.n_prefill, sp.n_long, sp.decode_qsl.data_ptr(), _ptr(sp.decode_index) if sp.num_decode_tokens else None,
+        sp.num_decode_tokens, max(1, sp.max_decode_q_len), sp.max_prefill_q_len,
+        N.current_stream_ptr() if stream is None else stream))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # A12 Ulysses repartition copies
 # ------------------------------------------------------------------------------------------------
 def ulysses_pack_qkv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, sp: int) -> torch.Tensor:

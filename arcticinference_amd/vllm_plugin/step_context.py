@@ -4,30 +4,51 @@ vLLM's Attention.forward sees device tensors only; the runner knows on the HOST 
 the step has (scheduler_output.num_scheduled_tokens).  aic_verify_attention_ex wants the batch partitioned by
 query length (short requests / long suffix drafts, include/arctic_hip.h), so the runner publishes the step's
 per-request query lengths here and every attention layer of the step reuses one partition built from them.
-One runner per process (vLLM worker), one step at a time: a module-level slot is the whole mechanism."""
+One runner per process (vLLM worker), one step at a time: a module-level slot is the whole mechanism.
+
+Steps with prefill chunks (a request of more than MAX_SPEC_LEN + 1 query tokens) go to aic_step_attention when the
+PREFILL_ENV switch is on (read once per step, in publish()); step_split() is its per-step partition."""
 from __future__ import annotations
 
+import os
 from typing import Dict, Optional, Tuple
 
 import numpy as np
 
+PREFILL_ENV = "ARCTIC_INFERENCE_HIP_PREFILL"   # 1: steps with prefill chunks on the HIP route too (default off)
+
 _q_lens: Optional[np.ndarray] = None
 _shift_mode: bool = False
+_prefill_on: bool = False
 _splits: Dict[Tuple[int, int], object] = {}     # (group size, device index) -> ops.split_requests(...) of this step
-calls = {"verify": 0, "fallback": 0}          # attention calls routed to the HIP kernel / left to vLLM's backend
+_step_splits: Dict[Tuple[int, int], object] = {}  # (group size, device index) -> ops.StepSplit of this step
+# attention calls routed to the HIP kernels (verify: all of them; prefill: those of them with prefill chunks) / left to
+# vLLM's backend
+calls = {"verify": 0, "fallback": 0, "prefill": 0}
+
+
+def prefill_switch() -> bool:
+    return os.environ.get(PREFILL_ENV, "0").strip().lower() in ("1", "true", "yes", "on")
 
 
 def publish(num_scheduled_tokens: np.ndarray, shift_mode: bool) -> None:
-    global _q_lens, _shift_mode
+    global _q_lens, _shift_mode, _prefill_on
     _q_lens = np.asarray(num_scheduled_tokens)
     _shift_mode = bool(shift_mode)
+    _prefill_on = prefill_switch()
     _splits.clear()
+    _step_splits.clear()
 
 
 def clear() -> None:
     global _q_lens
     _q_lens = None
     _splits.clear()
+    _step_splits.clear()
+
+
+def prefill_on() -> bool:
+    return _prefill_on
 
 
 def q_lens() -> Optional[np.ndarray]:
@@ -47,3 +68,31 @@ def request_split(group_size: int, device):
         from .. import ops
         _splits[key] = ops.split_requests(_q_lens, group_size, device)
     return _splits[key]
+
+
+def step_split(group_size: int, device):
+    """ops.StepSplit of the published step (three-way request lists + compact decode layout), or None when nothing is
+    published."""
+    if _q_lens is None:
+        return None
+    key = (group_size, device.index)
+    if key not in _step_splits:
+        from .. import ops
+        _step_splits[key] = ops.StepSplit(_q_lens, group_size, device)
+    return _step_splits[key]
+
+
+def route(max_query_len: int, q_lens, batch: int, prefill_on: bool, layer_ok: bool, capturing: bool) -> str:
+    """Which attention serves a call: "verify" (every request has at most MAX_SPEC_LEN + 1 query tokens: the verify
+    bodies, as before), "step" (prefill chunks in the step, served by aic_step_attention) or "fallback" (vLLM's
+    backend).  Prefill steps take the HIP route only with the switch on, on a layer the prefill body serves (head size
+    128, bf16 / fp8 cache, no window / sinks / alibi / soft-cap), with published q_lens that describe the call
+    (`batch` requests, the longest `max_query_len` tokens) and outside graph capture."""
+    from .runner_logic import MAX_SPEC_LEN
+    if max_query_len <= MAX_SPEC_LEN + 1:
+        return "verify"
+    if not (prefill_on and layer_ok) or capturing or q_lens is None:
+        return "fallback"
+    if len(q_lens) != batch or int(np.max(q_lens)) != int(max_query_len):
+        return "fallback"
+    return "step"

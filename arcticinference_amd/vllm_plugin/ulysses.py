@@ -12,8 +12,9 @@
 The group ALGEBRA is arcticinference_amd.ulysses.rank_groups() (pure, tested against the reference's tensor
 reshapes on CPU); this module only turns its rank lists into vLLM GroupCoordinators.  The attention patch is
 where this build differs from the reference on purpose: decode / verify steps (every request has at most
-MAX_SPEC_LEN + 1 query tokens) do not go to vLLM's attention backend but to aic_verify_attention_ex, and the
-copies around the all-to-alls are the fused HIP kernels of csrc/ulysses_pack.hip.
+MAX_SPEC_LEN + 1 query tokens) do not go to vLLM's attention backend but to aic_verify_attention_ex — and, with
+ARCTIC_INFERENCE_HIP_PREFILL=1, steps with prefill chunks go to aic_step_attention — and the copies around the
+all-to-alls are the fused HIP kernels of csrc/ulysses_pack.hip.
 """
 from __future__ import annotations
 
@@ -244,7 +245,10 @@ def build_ulysses_patches():
             meta = ctx.attn_metadata
             if isinstance(meta, dict):
                 meta = meta.get(self.layer_name)
-            if meta is None or getattr(meta, "max_query_len", 1 << 30) > MAX_SPEC_LEN + 1:
+            if meta is None:
+                return None
+            max_q = int(getattr(meta, "max_query_len", 1 << 30))
+            if max_q > MAX_SPEC_LEN + 1 and not step_context.prefill_on():
                 return None
             kv_cache = self.kv_cache[ctx.virtual_engine]
             if not _flash_layout(kv_cache, self.num_kv_heads, self.head_size) or self.head_size not in (64, 128):
@@ -259,6 +263,11 @@ def build_ulysses_patches():
                 return None
             fp8 = kv_cache.dtype in (torch.uint8, torch.float8_e4m3fn)
             if fp8 and self.head_size != 128:
+                return None
+            # steps with prefill chunks (ARCTIC_INFERENCE_HIP_PREFILL): aic_step_attention, on layers its prefill body serves
+            route = step_context.route(max_q, step_context.q_lens(), meta.seq_lens.numel(), step_context.prefill_on(),
+                                       self.head_size == 128 and window == 0 and sinks is None, capturing)
+            if route == "fallback":
                 return None
             n = meta.num_actual_tokens
             k_cache, v_cache = kv_cache[0], kv_cache[1]
@@ -277,6 +286,15 @@ def build_ulysses_patches():
             q = query[:n].unflatten(-1, (hq, D)) if query.dim() == 2 else query[:n]
             out = torch.empty((query.shape[0], hq * D), dtype=query.dtype, device=query.device)
             batch = meta.seq_lens.numel()
+            if route == "step":
+                ops.step_attention(q, k_cache, v_cache, meta.block_table, meta.seq_lens.to(torch.int32),
+                                   meta.query_start_loc.to(torch.int32), int(meta.max_seq_len), float(self.impl.scale),
+                                   step_split=step_context.step_split(hq // self.num_kv_heads, query.device),
+                                   out=out[:n].view(n, hq, D), k_scale=self._k_scale if fp8 else None,
+                                   v_scale=self._v_scale if fp8 else None)
+                step_context.calls["verify"] += 1
+                step_context.calls["prefill"] += 1
+                return out
             split = None
             if not capturing:
                 split = step_context.request_split(hq // self.num_kv_heads, query.device)

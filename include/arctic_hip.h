@@ -445,6 +445,38 @@ int aic_verify_attention_layers(const void* q, int64_t q_stride, int64_t q_layer
                                 int n_short, const int32_t* long_reqs, int n_long, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A5p  Whole-step attention with prefill chunks — what `self._orig_forward(q_, k_, v_)` reaches through vLLM's attention
+ *      backend for ANY step (ulysses.py:510): decodes, long drafts and prefill chunks (q_len > 33, chunked prefill and
+ *      the Ulysses SP prefill) in one call.  Same semantics, layouts and cache dtypes as aic_verify_attention; the
+ *      prefill part needs head_size 128 and at most 8 query heads per kv head.
+ *        req_lists: device int32[batch] = the short requests (n_short, q_len * Hq/Hkv <= 32 rows), then the prefill
+ *            requests (n_prefill), then the long drafts (n_long); together a partition of the batch, in any order of
+ *            the batch (ops.split_order3).
+ *        decode_query_start_loc: device int32[batch + 1], the decode rows' offsets in a compact layout in which every
+ *            prefill request has an empty range; decode_token_index: device int32[num_decode_tokens], token of the call
+ *            of each compact row (ops.decode_index).  max_decode_q_len bounds the decode requests (<= 33),
+ *            max_prefill_q_len the prefill requests.
+ *      The decode rows are gathered, served by the verify bodies as a compact call (n_prefill == 0: exactly
+ *      aic_verify_attention_ex on the call's own arrays, the decode arguments unused) and scattered back; the prefill
+ *      requests go through a flash-attention body (csrc/prefill_attn.hip).  Nothing of the decode part's workspace or
+ *      combine launch scales with the prefill tokens:
+ *        workspace >= aic_step_attention_workspace_bytes(num_decode_tokens, n_prefill, max_prefill_q_len, ...)
+ *                  <= the decode-only need (n_prefill = 0) + the prefill-only need (num_decode_tokens = 0)
+ *      for num_splits_max >= 2.  out_stride a multiple of 8 elements.  Not graph-capture safe with prefill requests
+ *      (host-side geometry).
+ * ---------------------------------------------------------------------------------------- */
+size_t aic_step_attention_workspace_bytes(int num_decode_tokens, int n_prefill, int max_prefill_q_len, int num_q_heads,
+                                          int num_kv_heads, int head_size, int num_splits_max);
+int aic_step_attention(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache, int64_t block_stride,
+                       int kv_dtype, const float* k_scale, const float* v_scale, const int32_t* block_table,
+                       int max_blocks_per_seq, const int32_t* seq_lens, const int32_t* query_start_loc, int batch,
+                       int num_tokens, int num_q_heads, int num_kv_heads, int head_size, int block_size, float sm_scale,
+                       void* out, int64_t out_stride, void* workspace, size_t workspace_bytes, int max_seq_len,
+                       const int32_t* req_lists, int n_short, int n_prefill, int n_long,
+                       const int32_t* decode_query_start_loc, const int32_t* decode_token_index, int num_decode_tokens,
+                       int max_decode_q_len, int max_prefill_q_len, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * A12  Ulysses head/sequence repartition — the copies around the two all-to-alls of
  *      UlyssesAttentionPatch.forward (ulysses.py:493-507, :513-517).  The collectives
  *      themselves stay torch.distributed (RCCL) calls in the Python layer.

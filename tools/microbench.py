@@ -266,6 +266,76 @@ def attn_long_phases(B=16, q_long=33, ctx=4096, Hq=32, Hkv=8, D=128, bs=16, n_sh
               f"K reads + score MFMAs issued {f(3):5.0f} | soft-max {f(4):5.0f} | V reads + PV MFMAs issued {f(5):5.0f};  prologue {float(np.median(t[m, 0])):6.0f}")
 
 
+def _prefill_case(q_lens, ctxs, Hq, Hkv, D=128, bs=16, kv8=False):
+    """Paged caches + q for a step of requests with the given query lengths and contexts (random data)."""
+    nblk = [(c + bs - 1) // bs for c in ctxs]
+    nb = sum(nblk)
+    if kv8:
+        raw = torch.randint(0, 256, (2, nb, bs, Hkv, D), dtype=torch.uint8, device=dev)
+        raw[(raw & 0x7f) == 0x7f] = 0x30
+        kv = raw.view(torch.float8_e4m3fn)
+        sc = torch.full((1,), 0.02, dtype=torch.float32, device=dev)
+        kw = dict(k_scale=sc, v_scale=sc)
+    else:
+        kv = torch.randn(2, nb, bs, Hkv, D, device=dev, dtype=torch.bfloat16)
+        kw = {}
+    perm = torch.randperm(nb, device=dev).to(torch.int32)
+    bt = torch.zeros(len(ctxs), max(nblk), dtype=torch.int32, device=dev)
+    k = 0
+    for i, n in enumerate(nblk):
+        bt[i, :n] = perm[k:k + n]
+        k += n
+    T = sum(q_lens)
+    q = torch.randn(T, Hq, D, device=dev, dtype=torch.bfloat16)
+    seq = torch.tensor(ctxs, dtype=torch.int32, device=dev)
+    qsl = torch.tensor(np.concatenate([[0], np.cumsum(q_lens)]).astype(np.int32), device=dev)
+    return q, kv, bt, seq, qsl, kw
+
+
+def _visible_keys(q_lens, ctxs, decode_too=True):
+    return sum(sum(c - n + i + 1 for i in range(n)) for n, c in zip(q_lens, ctxs) if decode_too or n > 33)
+
+
+def prefill(q_lens, ctxs, Hq=32, Hkv=8, D=128, bs=16, kv8=False, label="", sdpa=False):
+    """aic_step_attention on one step: us per call and TFLOP/s with FLOPs = 4 D Hq sum(visible keys)."""
+    q, kv, bt, seq, qsl, kw = _prefill_case(q_lens, ctxs, Hq, Hkv, D, bs, kv8)
+    split = ops.StepSplit(q_lens, Hq // Hkv, dev)
+    out = torch.empty_like(q)
+
+    def f():
+        ops.step_attention(q, kv[0], kv[1], bt, seq, qsl, max(ctxs), D ** -0.5, step_split=split, out=out, **kw)
+    us = timeit(f, iters=10, warm=2)
+    fl = 4.0 * D * Hq * _visible_keys(q_lens, ctxs)
+    print(f"prefill{' fp8kv' if kv8 else ''} {label} Hq={Hq} Hkv={Hkv} bs={bs}: {us:9.1f} us  {fl / us / 1e6:7.1f} TFLOP/s")
+    if sdpa:   # reference point: torch SDPA on K/V gathered into contiguous tensors (single request, bf16 only)
+        (n,), (c,) = q_lens, ctxs
+        nblk = (c + bs - 1) // bs
+        K = kv[0][bt[0, :nblk].long()].reshape(-1, Hkv, D)[:c].transpose(0, 1).repeat_interleave(Hq // Hkv, 0)
+        V = kv[1][bt[0, :nblk].long()].reshape(-1, Hkv, D)[:c].transpose(0, 1).repeat_interleave(Hq // Hkv, 0)
+        Q = q.transpose(0, 1)
+        mask = torch.arange(c, device=dev)[None, :] <= (torch.arange(n, device=dev)[:, None] + c - n)
+        us2 = timeit(lambda: torch.nn.functional.scaled_dot_product_attention(Q, K, V, attn_mask=mask), iters=10, warm=2)
+        print(f"  torch sdpa (contiguous K/V, explicit mask)  : {us2:9.1f} us  {fl / us2 / 1e6:7.1f} TFLOP/s")
+    return us
+
+
+def prefill_suite():
+    for kv8 in (False, True):
+        for n, c in ((512, 4096), (2048, 4096), (2048, 8192)):
+            prefill([n], [c], kv8=kv8, label=f"llama-8b chunk {n} ctx {c}", sdpa=not kv8)
+    for c in (16384, 32768):        # Llama-70B SP = 8 slice: one kv head per rank
+        prefill([8192], [c], Hq=8, Hkv=1, label=f"llama-70b sp8 chunk 8192 ctx {c}")
+        prefill([8192], [c], Hq=8, Hkv=1, kv8=True, label=f"llama-70b sp8 chunk 8192 ctx {c}")
+    # mixed call: 63 decoding requests (q_len 1..33) at ctx ~4096 + one 2048-token chunk (the last of a 4096-token prompt)
+    rng = np.random.default_rng(0)
+    dq = [int(x) for x in rng.integers(1, 34, 63)]
+    dc = [int(x) for x in rng.integers(3968, 4224, 63)]
+    mixed = prefill(dq[:31] + [2048] + dq[31:], dc[:31] + [4096] + dc[31:], label="mixed 63 decodes + chunk 2048")
+    dec = prefill(dq, dc, label="decode-only 63")
+    chunk = prefill([2048], [4096], label="chunk-only 2048")
+    print(f"mixed / (decode-only + chunk-only) = {mixed / (dec + chunk):.3f}")
+
+
 def lstm(B, fp8=True):
     from arcticinference_amd.speculator import ArcticLSTMSpeculator, LSTMSpeculatorConfig, random_lstm_weights
     cfg = LSTMSpeculatorConfig(vocab_size=128256, input_hidden_dim=4096)
@@ -517,6 +587,8 @@ if __name__ == "__main__":
                         print("hpw %d splits %2d: " % (hpw, sp), end="")
                         attn_mix(ns, nl, Hq=4 * Hkv, Hkv=Hkv)
         N.lib().aic_debug_attn_layout(0, 0)
+    if "prefill" in what:       # aic_step_attention: prefill chunks, the SP = 8 slice, a mixed step
+        prefill_suite()
     if "lstm" in what:
         lstm(64)
         lstm(32)
