@@ -158,6 +158,10 @@ _SIGNATURES = {
                                    c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
                                    c_int64, c_void_p, c_size_t, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                    c_int, c_int, c_int, c_void_p]),
+    "aic_step_attention_win": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
+                                       c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                       c_float, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_void_p, c_int, c_int,
+                                       c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "aic_step_build": (c_int, [c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                                c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "aic_step_parse": (c_int, [c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p,

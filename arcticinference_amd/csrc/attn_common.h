@@ -38,6 +38,17 @@ __device__ __forceinline__ int v_tile_off(int t, int ch) {
   return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
 }
 
+// Image of a 32-token tile for head size D: D = 128 is v_tile_off; D = 64 (128-byte rows, 8 chunks) XORs the chunk
+// with the row (the secondary head size: correct and DMA-fillable first, bank-optimal second).
+template <int D>
+__device__ __forceinline__ int tile_off(int t, int ch) {
+  if constexpr (D == 128) {
+    return v_tile_off(t, ch);
+  } else {
+    return 128 * t + 16 * (ch ^ (t & 7));
+  }
+}
+
 // Lanes c16 + 16 g (g = 0..3) hold the same query row.  gfx950's row / half swaps combine them on the VALU
 // (ds_bpermute costs an LDS round trip per step, and the long-draft kernel is VALU/latency bound).  The
 // s_nops are the VALU-write -> permlane-swap -> VALU-read hazards the assembler does not see inside asm.

@@ -24,6 +24,9 @@
 //     and re-reads its K/V through that XCD's L2;
 //   * a call with fewer workgroups than CUs (a short chunk, an SP = 8 slice with one kv head) splits the key range and
 //     merges the partials in a second launch, as the decode path does.
+// gpt-oss layers (aic_step_attention_win): head size 64 halves the Q / K fragments and the output tiles and uses the
+// verify bodies' 128-byte-row tile image (tile_off<64>); a sliding window starts a workgroup's key range at the tile of
+// its first row's first key and adds a lower edge to the mask; a sink is the (max, sum) = (sink, 1) start of split 0.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -35,7 +38,6 @@
 namespace aic {
 namespace {
 
-constexpr int kPfD = 128;                       // head size
 constexpr int kPfWaves = 4;
 constexpr int kPfMT = 2;                        // 16-row MFMA tiles per wave
 constexpr int kPfRows = kPfWaves * kPfMT * 16;  // query rows (token x head of the group) per workgroup
@@ -55,7 +57,7 @@ struct PrefillParams {
   const float* k_scale;  // fp8 cache: per-tensor scales (device scalars)
   const float* v_scale;
   uint16_t* out;
-  float* ws_o;   // split mode: [n_splits][n_wg][kPfRows][kPfD] unnormalised partials
+  float* ws_o;   // split mode: [n_splits][n_wg][kPfRows][head size] unnormalised partials
   float* ws_ml;  // [n_splits][n_wg][kPfRows][2] {max (natural log units), sum}
   int64_t q_stride;
   int64_t out_stride;
@@ -70,6 +72,10 @@ struct PrefillParams {
   int n_wg;      // n_req * n_qb * num_kv_heads
   int n_splits;
   float sm_scale;
+  // gpt-oss layers, as in the verify bodies.  window > 0: query position p sees keys p - window + 1 .. p only.  sinks
+  // (f32 [num_q_heads] or null): one extra logit per head, the initial (max, sum = 1) state of split 0 of every row.
+  int window;
+  const float* sinks;
 };
 
 // workgroup index (without the split) -> (kv head, request slot, query block): kv head fastest, last query block first
@@ -85,12 +91,18 @@ __device__ __forceinline__ PfItem pf_item(const PrefillParams& P, int wgi) {
   return it;
 }
 
-template <bool KV8>
+// D = head size: 128 (bf16 or fp8 cache) or 64 (bf16 cache; the verify bodies' rule).  WIN: the layer has a sliding
+// window (P.window > 0).  Without one the window terms fold away and the tile loop is the plain causal one: they cost
+// the D = 128 body ~2.5 % when kept as runtime tests (measured on the Llama-8B 2048-token chunk at ctx 4096).
+template <int D, bool KV8, bool WIN>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) prefill_attn_kernel(PrefillParams P) {
-  constexpr int DT = kPfD / 16;
+  static_assert(D == 128 || (D == 64 && !KV8), "head size 128, or 64 with a bf16 cache");
+  constexpr int DT = D / 16;   // 16-wide output tiles
+  constexpr int NS = D / 32;   // k-steps of mfma_f32_16x16x32_bf16 per S tile
   constexpr int ES = KV8 ? 1 : 2;
-  // [buffer][K, V] 32-token tiles in the verify bodies' image (v_tile_off): read row-wise for K, transposed for V
-  __shared__ uint4 lds[2][2][kTile * 16];
+  constexpr bool ONE_CHUNK = KV8 || D == 64;  // a token row of one head is 128 bytes: one 16-byte chunk of K and of V per thread
+  // [buffer][K, V] 32-token tiles in the verify bodies' image (tile_off<D>): read row-wise for K, transposed for V
+  __shared__ uint4 lds[2][2][kTile * D / 8];
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -108,46 +120,53 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
   if (blk_row0 >= n_rows) return;  // a shorter request of the call: no such block (whole workgroup)
   const int ctx0 = ctx - q_len;    // position of the request's first query token
   const int kv_end = ctx0 + (min(blk_row0 + kPfRows, n_rows) - 1) / G + 1;  // keys the block's last row sees
+  const int wnd = WIN ? P.window : (1 << 30);
+  // sliding window: the block's first row sees nothing below key ctx0 + blk_row0 / G - window + 1, nor does any later row
+  const int key_lo = WIN ? max(0, ctx0 + blk_row0 / G - wnd + 1) : 0;
+  const int tile_lo = key_lo / kTile;
   const int tiles = (kv_end + kTile - 1) / kTile;
-  const int tps = (tiles + P.n_splits - 1) / P.n_splits;
-  const int t_first = split * tps, t_last = min(tiles, t_first + tps);
+  const int tps = (tiles - tile_lo + P.n_splits - 1) / P.n_splits;
+  const int t_first = tile_lo + split * tps, t_last = min(tiles, t_first + tps);
 
-  // this wave's rows: keys up to w_lim_lo are visible to all of them, none beyond w_lim_hi to any
+  // this wave's rows: keys up to w_lim_lo are visible to all of them, none beyond w_lim_hi to any; with a window, keys
+  // at or below w_lim_lo - window are visible to none of them, keys above w_lim_hi - window to all
   const int w_row0 = blk_row0 + wave * (kPfMT * 16);
   const bool wave_live = w_row0 < n_rows;
   const int w_lim_lo = ctx0 + w_row0 / G;
   const int w_lim_hi = ctx0 + (min(w_row0 + kPfMT * 16, n_rows) - 1) / G;
 
   // ---- query fragments (B operand of S^T = K Q^T): lane (row c16, k-group g), d = 32 s + 8 g + j ------------
-  uint4 qf[kPfMT][4];
-  int lim[kPfMT];  // last key a lane's row sees
+  // ---- and the row state: (max, sum) = (-inf, 0), or (sink, 1) in split 0 of a layer with sinks
+  uint4 qf[kPfMT][NS];
+  int lim[kPfMT];  // last key a lane's row sees (the first is lim - window + 1)
+  float m_run[kPfMT], l_run[kPfMT];
+  f32x4 o_acc[kPfMT][DT];
 #pragma unroll
   for (int mt = 0; mt < kPfMT; ++mt) {
     const int rc = min(w_row0 + mt * 16 + c16, n_rows - 1);
     const int pos = rc / G, gq = rc - pos * G;
     lim[mt] = ctx0 + pos;
-    const uint16_t* qrow = P.q + static_cast<int64_t>(q0 + pos) * P.q_stride + static_cast<int64_t>(h * G + gq) * kPfD;
+    const uint16_t* qrow = P.q + static_cast<int64_t>(q0 + pos) * P.q_stride + static_cast<int64_t>(h * G + gq) * D;
 #pragma unroll
-    for (int s = 0; s < 4; ++s) qf[mt][s] = *reinterpret_cast<const uint4*>(qrow + 32 * s + 8 * g);
+    for (int s = 0; s < NS; ++s) qf[mt][s] = *reinterpret_cast<const uint4*>(qrow + 32 * s + 8 * g);
+    m_run[mt] = -INFINITY;
+    l_run[mt] = 0.0f;
+    if (P.sinks != nullptr && split == 0) {
+      m_run[mt] = P.sinks[h * G + gq] * kLog2e;  // log2 units, like the scaled scores; not multiplied by sm_scale
+      l_run[mt] = g == 0 ? 1.0f : 0.0f;          // l_run is this lane's share of the row's sum: one lane carries the 1
+    }
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) o_acc[mt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   const float scale_log2 = P.sm_scale * kLog2e * (KV8 ? *P.k_scale : 1.0f);
   const float inv_scale = 1.0f / scale_log2;
   const float out_scale = KV8 ? *P.v_scale : 1.0f;
 
-  float m_run[kPfMT], l_run[kPfMT];
-  f32x4 o_acc[kPfMT][DT];
-#pragma unroll
-  for (int mt = 0; mt < kPfMT; ++mt) {
-    m_run[mt] = -INFINITY;
-    l_run[mt] = 0.0f;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) o_acc[mt][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-
-  // ---- tile staging: bf16 = two 16-byte chunks of K and of V per thread (tokens t/16 and 16 + t/16, chunk t%16);
-  // fp8 = one of each (token t/8, 8-byte halves of chunk t%8 -> bf16 chunks 2 (t%8), 2 (t%8) + 1).  A 16-token group
-  // never straddles two pages (block_size is a multiple of 16): its page lookup is one scalar per group.
-  const int64_t kv_row = static_cast<int64_t>(Hkv) * kPfD;  // elements between consecutive tokens of a page
+  // ---- tile staging: bf16 D = 128 = two 16-byte chunks of K and of V per thread (tokens t/16 and 16 + t/16, chunk
+  // t%16); fp8 = one of each (token t/8, 8-byte halves of chunk t%8 -> bf16 chunks 2 (t%8), 2 (t%8) + 1); bf16 D = 64 =
+  // one of each (token t/8, chunk t%8).  A 16-token group never straddles two pages (block_size is a multiple of 16):
+  // its page lookup is one scalar per group.
+  const int64_t kv_row = static_cast<int64_t>(Hkv) * D;  // elements between consecutive tokens of a page
   const unsigned row_bytes = static_cast<unsigned>(kv_row) * ES;
   const_i32_ptr btab = (const_i32_ptr)(P.block_table + static_cast<int64_t>(req) * P.max_blocks);
   const int last_group = (ctx - 1) & ~15;
@@ -157,17 +176,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
     const unsigned f = static_cast<unsigned>(first), bs = static_cast<unsigned>(P.block_size);
     const unsigned pg = P.bs_shift >= 0 ? f >> P.bs_shift : f / bs;
     const unsigned po = f - pg * bs;
-    return static_cast<int64_t>(btab[pg]) * P.block_stride + static_cast<int64_t>(po) * kv_row + h * kPfD;
+    return static_cast<int64_t>(btab[pg]) * P.block_stride + static_cast<int64_t>(po) * kv_row + h * D;
   };
   auto load_tile = [&](int tt) {
     const int f0 = min(tt, last_group), f1 = min(tt + 16, last_group);
     const int64_t b0 = group_base(f0), b1 = group_base(f1);
-    if (KV8) {
+    if (ONE_CHUNK) {
       const int ti = tid >> 3, ch = tid & 7;
       const int first = ti < 16 ? f0 : f1;
       const int64_t base = ti < 16 ? b0 : b1;
       const unsigned off = static_cast<unsigned>(min(tt + ti, ctx - 1) - first);
-      const size_t byte = static_cast<size_t>(base) + __umul24(off, row_bytes) + 16u * ch;
+      const size_t byte = static_cast<size_t>(base) * ES + __umul24(off, row_bytes) + 16u * ch;
       kr0 = ld_kv16(P.k_cache + byte);
       vr0 = ld_kv16(P.v_cache + byte);
     } else {
@@ -182,15 +201,30 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
       vr1 = ld_kv16(P.v_cache + y1);
     }
   };
-  auto store_tile = [&](int buf) {
+  // V of keys below every row's window (the first tile of a windowed range) is staged as zeros: their weights are 0,
+  // and a page that lies wholly below the windows may then hold anything, NaN included, without reaching the output
+  auto store_tile = [&](int buf, int tt) {
     char* kt = reinterpret_cast<char*>(lds[buf][0]);
     char* vt = reinterpret_cast<char*>(lds[buf][1]);
+    if (WIN && tt < key_lo) {
+      const uint4 z = make_uint4(0, 0, 0, 0);
+      if (ONE_CHUNK) {
+        if (tt + (tid >> 3) < key_lo) vr0 = z;
+      } else {
+        if (tt + (tid >> 4) < key_lo) vr0 = z;
+        if (tt + 16 + (tid >> 4) < key_lo) vr1 = z;
+      }
+    }
     if (KV8) {
       const int ti = tid >> 3, ch = 2 * (tid & 7);
       *reinterpret_cast<bf16x8*>(kt + v_tile_off(ti, ch)) = fp8x8_to_bf16x8(kr0.x, kr0.y);
       *reinterpret_cast<bf16x8*>(kt + v_tile_off(ti, ch + 1)) = fp8x8_to_bf16x8(kr0.z, kr0.w);
       *reinterpret_cast<bf16x8*>(vt + v_tile_off(ti, ch)) = fp8x8_to_bf16x8(vr0.x, vr0.y);
       *reinterpret_cast<bf16x8*>(vt + v_tile_off(ti, ch + 1)) = fp8x8_to_bf16x8(vr0.z, vr0.w);
+    } else if (D == 64) {
+      const int ti = tid >> 3, ch = tid & 7;
+      *reinterpret_cast<uint4*>(kt + tile_off<64>(ti, ch)) = kr0;
+      *reinterpret_cast<uint4*>(vt + tile_off<64>(ti, ch)) = vr0;
     } else {
       const int ti = tid >> 4, ch = tid & 15;
       *reinterpret_cast<uint4*>(kt + v_tile_off(ti, ch)) = kr0;
@@ -204,18 +238,19 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
   auto compute_tile = [&](int buf, int tt) {
     const char* kt = reinterpret_cast<const char*>(lds[buf][0]);
     const char* vt = reinterpret_cast<const char*>(lds[buf][1]);
-    bf16x8 kf[2][4];  // A operand: key 16 th + c16, d = 32 s + 8 g + j
+    bf16x8 kf[2][NS];  // A operand: key 16 th + c16, d = 32 s + 8 g + j
 #pragma unroll
     for (int th = 0; th < 2; ++th)
 #pragma unroll
-      for (int s = 0; s < 4; ++s) kf[th][s] = *reinterpret_cast<const bf16x8*>(kt + v_tile_off(16 * th + c16, 4 * s + g));
-    const bool need_mask = tt + kTile - 1 > w_lim_lo;
+      for (int s = 0; s < NS; ++s) kf[th][s] = *reinterpret_cast<const bf16x8*>(kt + tile_off<D>(16 * th + c16, 4 * s + g));
+    // the tile crosses the causal edge of a row of the wave, or (window) holds a key at or below a row's lim - window
+    const bool need_mask = tt + kTile - 1 > w_lim_lo || (WIN && tt <= w_lim_hi - wnd);
     bf16x8 pf[kPfMT], pl[kPfMT];  // P = head + tail (bf16 each): one bf16 P would put 2^-9 on every weight
 #pragma unroll
     for (int mt = 0; mt < kPfMT; ++mt) {
       f32x4 a0 = f32x4{0.f, 0.f, 0.f, 0.f}, a1 = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int s = 0; s < 4; ++s) {
+      for (int s = 0; s < NS; ++s) {
         a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[0][s], __builtin_bit_cast(bf16x8, qf[mt][s]), a0, 0, 0, 0);
         a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[1][s], __builtin_bit_cast(bf16x8, qf[mt][s]), a1, 0, 0, 0);
       }
@@ -228,8 +263,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
       }
       if (need_mask) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if (tt + 16 * (e >> 2) + 4 * g + (e & 3) > lim[mt]) sc[e] = -INFINITY;
+        for (int e = 0; e < 8; ++e) {
+          const int key = tt + 16 * (e >> 2) + 4 * g + (e & 3);
+          if (key > lim[mt] || (WIN && key <= lim[mt] - wnd)) sc[e] = -INFINITY;
+        }
       }
       float lmax = sc[0];
 #pragma unroll
@@ -260,8 +297,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
     const int q4 = c16 >> 2, p4 = c16 & 3;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
-      const char* a_lo = vt + v_tile_off(4 * g + q4, 2 * dt + (p4 >> 1)) + 8 * (p4 & 1);
-      const char* a_hi = vt + v_tile_off(16 + 4 * g + q4, 2 * dt + (p4 >> 1)) + 8 * (p4 & 1);
+      const char* a_lo = vt + tile_off<D>(4 * g + q4, 2 * dt + (p4 >> 1)) + 8 * (p4 & 1);
+      const char* a_hi = vt + tile_off<D>(16 + 4 * g + q4, 2 * dt + (p4 >> 1)) + 8 * (p4 & 1);
       const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(const_cast<char*>(a_lo)));
       const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(const_cast<char*>(a_hi)));
       typedef __attribute__((ext_vector_type(8))) short s16x8;
@@ -277,15 +314,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
 
   if (t_first < t_last) {
     load_tile(t_first * kTile);
-    store_tile(0);
+    store_tile(0, t_first * kTile);
     __syncthreads();
     for (int t = t_first; t < t_last; ++t) {
       const int buf = (t - t_first) & 1;
       const int tt = t * kTile;
       const bool more = t + 1 < t_last;
       if (more) load_tile(tt + kTile);                        // in flight during the tile's MFMAs
-      if (wave_live && tt <= w_lim_hi) compute_tile(buf, tt);  // tiles past all of the wave's rows: nothing to do
-      if (more) store_tile(buf ^ 1);                          // last read in the previous iteration, before its barrier
+      // tiles past all of the wave's rows, or below all of their windows: nothing to do
+      if (wave_live && tt <= w_lim_hi && (!WIN || tt + kTile - 1 > w_lim_lo - wnd)) compute_tile(buf, tt);
+      if (more) store_tile(buf ^ 1, tt + kTile);                          // last read in the previous iteration, before its barrier
       __syncthreads();
     }
   }
@@ -299,7 +337,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
     const int pos = rr / G, gq = rr - pos * G;
     if (P.n_splits == 1) {
       const float inv = l > 0.0f ? out_scale / l : 0.0f;
-      uint16_t* op = P.out + static_cast<int64_t>(q0 + pos) * P.out_stride + static_cast<int64_t>(h * G + gq) * kPfD + 4 * g;
+      uint16_t* op = P.out + static_cast<int64_t>(q0 + pos) * P.out_stride + static_cast<int64_t>(h * G + gq) * D + 4 * g;
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
         const uint32_t lo = static_cast<uint32_t>(f32_to_bf16(o_acc[mt][dt][0] * inv)) |
@@ -310,7 +348,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
       }
     } else {
       const int64_t slot = (static_cast<int64_t>(split) * P.n_wg + wgi) * kPfRows + (rr - blk_row0);
-      float* op = P.ws_o + slot * kPfD + 4 * g;
+      float* op = P.ws_o + slot * D + 4 * g;
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt)
         *reinterpret_cast<float4*>(op + dt * 16) = make_float4(o_acc[mt][dt][0] * out_scale, o_acc[mt][dt][1] * out_scale,
@@ -320,9 +358,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
   }
 }
 
-// Merge of the split partials: one wave per row of the prefill grid (lane = two elements of the head dimension).
+// Merge of the split partials: one wave per row of the prefill grid (lane = two elements of the head dimension; D = 64
+// leaves the upper half of the wave idle).
+template <int D>
 __global__ void __launch_bounds__(256) prefill_combine_kernel(PrefillParams P) {
   const int lane = threadIdx.x & 63;
+  if (2 * lane >= D) return;
   const int64_t row = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
   const int wgi = static_cast<int>(row / kPfRows), r = static_cast<int>(row - static_cast<int64_t>(wgi) * kPfRows);
   if (wgi >= P.n_wg) return;
@@ -342,13 +383,13 @@ __global__ void __launch_bounds__(256) prefill_combine_kernel(PrefillParams P) {
     const float2 ml = *reinterpret_cast<const float2*>(P.ws_ml + slot * 2);
     if (ml.x == -INFINITY) continue;  // a split whose keys this row does not see
     const float w = __expf(ml.x - M);
-    const float2 o = *reinterpret_cast<const float2*>(P.ws_o + slot * kPfD + 2 * lane);
+    const float2 o = *reinterpret_cast<const float2*>(P.ws_o + slot * D + 2 * lane);
     L += w * ml.y;
     acc0 += w * o.x;
     acc1 += w * o.y;
   }
   const float inv = L > 0.0f ? 1.0f / L : 0.0f;
-  uint16_t* op = P.out + static_cast<int64_t>(q0 + pos) * P.out_stride + static_cast<int64_t>(it.h * G + gq) * kPfD + 2 * lane;
+  uint16_t* op = P.out + static_cast<int64_t>(q0 + pos) * P.out_stride + static_cast<int64_t>(it.h * G + gq) * D + 2 * lane;
   *reinterpret_cast<uint32_t*>(op) =
       static_cast<uint32_t>(f32_to_bf16(acc0 * inv)) | (static_cast<uint32_t>(f32_to_bf16(acc1 * inv)) << 16);
 }
@@ -367,16 +408,19 @@ __global__ void __launch_bounds__(256) step_rows_kernel(const char* __restrict__
 }
 
 // Geometry of the prefill grid of a call: workgroups without the split, and the split count.  The workspace query
-// (which knows no context length) takes the largest split count the call could choose.
+// (which knows no context length, nor the window) takes the largest split count the call could choose.  With a sliding
+// window a workgroup reads at most window + its kPfRows / G tokens + one tile of rounding, whatever the context: the
+// split count follows that key count.
 struct PfGrid {
   int n_qb, n_wg, n_splits;
 };
-PfGrid pf_grid(int n_prefill, int max_prefill_q_len, int num_q_heads, int num_kv_heads, int max_seq_len) {
+PfGrid pf_grid(int n_prefill, int max_prefill_q_len, int num_q_heads, int num_kv_heads, int max_seq_len, int window = 0) {
   PfGrid gr;
   const int G = num_q_heads / num_kv_heads;
   gr.n_qb = static_cast<int>((static_cast<int64_t>(max_prefill_q_len) * G + kPfRows - 1) / kPfRows);
   gr.n_wg = n_prefill * gr.n_qb * num_kv_heads;
   gr.n_splits = 1;
+  if (max_seq_len > 0 && window > 0) max_seq_len = std::min(max_seq_len, window + kPfRows / G + kTile);
   if (gr.n_wg < kPfTargetWgs) {
     int s = std::min(kPfMaxSplits, kPfTargetWgs / std::max(1, gr.n_wg));
     if (max_seq_len > 0) s = std::min(s, std::max(1, (max_seq_len + kTile - 1) / kTile / kPfMinSplitTiles));
@@ -385,15 +429,32 @@ PfGrid pf_grid(int n_prefill, int max_prefill_q_len, int num_q_heads, int num_kv
   return gr;
 }
 
-size_t pf_partial_bytes(const PfGrid& gr) {
+size_t pf_partial_bytes(const PfGrid& gr, int head_size) {
   if (gr.n_splits <= 1) return 0;
   const size_t slots = static_cast<size_t>(gr.n_splits) * gr.n_wg * kPfRows;
-  return (slots * (kPfD + 2) * sizeof(float) + 255) & ~static_cast<size_t>(255);
+  return (slots * (head_size + 2) * sizeof(float) + 255) & ~static_cast<size_t>(255);
 }
 
-size_t pf_workspace_bytes(int n_prefill, int max_prefill_q_len, int num_q_heads, int num_kv_heads) {
+size_t pf_workspace_bytes(int n_prefill, int max_prefill_q_len, int num_q_heads, int num_kv_heads, int head_size) {
   if (n_prefill <= 0) return 0;
-  return pf_partial_bytes(pf_grid(n_prefill, max_prefill_q_len, num_q_heads, num_kv_heads, 0)) + 256;
+  return pf_partial_bytes(pf_grid(n_prefill, max_prefill_q_len, num_q_heads, num_kv_heads, 0), head_size) + 256;
+}
+
+template <int D, bool WIN>
+int launch_prefill(const PrefillParams& P, bool kv8, dim3 grid, hipStream_t s) {
+  if constexpr (D == 128) {
+    if (kv8)
+      hipLaunchKernelGGL((prefill_attn_kernel<128, true, WIN>), grid, dim3(256), 0, s, P);
+    else
+      hipLaunchKernelGGL((prefill_attn_kernel<128, false, WIN>), grid, dim3(256), 0, s, P);
+  } else {
+    hipLaunchKernelGGL((prefill_attn_kernel<D, false, WIN>), grid, dim3(256), 0, s, P);
+  }
+  int rc = launch_status("prefill_attn_kernel");
+  if (rc != AIC_OK || P.n_splits == 1) return rc;
+  const int64_t rows = static_cast<int64_t>(P.n_wg) * kPfRows;
+  hipLaunchKernelGGL(prefill_combine_kernel<D>, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), 0, s, P);
+  return launch_status("prefill_combine_kernel");
 }
 
 }  // namespace
@@ -411,7 +472,7 @@ size_t aic_step_attention_workspace_bytes(int num_decode_tokens, int n_prefill, 
   if (num_decode_tokens > 0)  // a mixed call stages the decode rows in one split's worth of the decode workspace
     dec = aic_verify_attention_workspace_bytes(num_decode_tokens, num_q_heads, head_size,
                                                n_prefill > 0 ? std::max(splits, 2) : splits);
-  return dec + pf_workspace_bytes(n_prefill, max_prefill_q_len, num_q_heads, num_kv_heads);
+  return dec + pf_workspace_bytes(n_prefill, max_prefill_q_len, num_q_heads, num_kv_heads, head_size);
 }
 
 int aic_step_attention(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache, int64_t block_stride,
@@ -422,17 +483,35 @@ int aic_step_attention(const void* q, int64_t q_stride, const void* k_cache, con
                        const int32_t* req_lists, int n_short, int n_prefill, int n_long,
                        const int32_t* decode_query_start_loc, const int32_t* decode_token_index, int num_decode_tokens,
                        int max_decode_q_len, int max_prefill_q_len, void* stream) {
+  return aic_step_attention_win(q, q_stride, k_cache, v_cache, block_stride, kv_dtype, k_scale, v_scale, block_table,
+                                max_blocks_per_seq, seq_lens, query_start_loc, batch, num_tokens, num_q_heads, num_kv_heads,
+                                head_size, block_size, sm_scale, out, out_stride, workspace, workspace_bytes, max_seq_len,
+                                req_lists, n_short, n_prefill, n_long, decode_query_start_loc, decode_token_index,
+                                num_decode_tokens, max_decode_q_len, max_prefill_q_len, 0, nullptr, stream);
+}
+
+int aic_step_attention_win(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache, int64_t block_stride,
+                           int kv_dtype, const float* k_scale, const float* v_scale, const int32_t* block_table,
+                           int max_blocks_per_seq, const int32_t* seq_lens, const int32_t* query_start_loc, int batch,
+                           int num_tokens, int num_q_heads, int num_kv_heads, int head_size, int block_size,
+                           float sm_scale, void* out, int64_t out_stride, void* workspace, size_t workspace_bytes,
+                           int max_seq_len, const int32_t* req_lists, int n_short, int n_prefill, int n_long,
+                           const int32_t* decode_query_start_loc, const int32_t* decode_token_index,
+                           int num_decode_tokens, int max_decode_q_len, int max_prefill_q_len, int sliding_window,
+                           const float* sinks, void* stream) {
   if (batch == 0 || num_tokens == 0) return AIC_OK;
+  AIC_REQUIRE(sliding_window >= 0, "sliding_window must be >= 0 (0 = none)");
   AIC_REQUIRE(req_lists && n_short >= 0 && n_prefill >= 0 && n_long >= 0 && n_short + n_prefill + n_long == batch,
               "short / prefill / long request lists must partition the batch");
   const int32_t* short_reqs = req_lists;
   const int32_t* prefill_reqs = req_lists + n_short;
   const int32_t* long_reqs = req_lists + n_short + n_prefill;
-  if (n_prefill == 0)  // a decode step: exactly aic_verify_attention_ex
-    return aic_verify_attention_ex(q, q_stride, k_cache, v_cache, block_stride, kv_dtype, k_scale, v_scale, block_table,
-                                   max_blocks_per_seq, seq_lens, query_start_loc, batch, num_tokens, max_decode_q_len,
-                                   num_q_heads, num_kv_heads, head_size, block_size, sm_scale, out, out_stride, workspace,
-                                   workspace_bytes, max_seq_len, short_reqs, n_short, long_reqs, n_long, stream);
+  if (n_prefill == 0)  // a decode step: exactly aic_verify_attention_win
+    return aic_verify_attention_win(q, q_stride, k_cache, v_cache, block_stride, kv_dtype, k_scale, v_scale, block_table,
+                                    max_blocks_per_seq, seq_lens, query_start_loc, batch, num_tokens, max_decode_q_len,
+                                    num_q_heads, num_kv_heads, head_size, block_size, sm_scale, out, out_stride, workspace,
+                                    workspace_bytes, max_seq_len, short_reqs, n_short, long_reqs, n_long, sliding_window,
+                                    sinks, stream);
 
   AIC_REQUIRE(q && k_cache && v_cache && block_table && seq_lens && query_start_loc && out && workspace,
               "null pointer argument to aic_step_attention");
@@ -440,15 +519,16 @@ int aic_step_attention(const void* q, int64_t q_stride, const void* k_cache, con
               "num_q_heads must be a positive multiple of num_kv_heads");
   AIC_REQUIRE(num_q_heads / num_kv_heads <= 8, "prefill body: at most 8 query heads per kv head");
   AIC_REQUIRE(max_prefill_q_len > 0 && max_seq_len > 0 && max_blocks_per_seq > 0, "non-positive size argument");
-  if (head_size != kPfD) {
-    set_error("prefill body: head_size %d not supported (128)", head_size);
-    return AIC_ERR_UNSUPPORTED;
-  }
   if (kv_dtype != AIC_DT_BF16 && kv_dtype != AIC_DT_FP8_E4M3) {
     set_error("kv cache dtype %d not supported (bf16 or fp8 e4m3)", kv_dtype);
     return AIC_ERR_UNSUPPORTED;
   }
   const bool kv8 = kv_dtype == AIC_DT_FP8_E4M3;
+  if (head_size != 128 && !(head_size == 64 && !kv8)) {
+    set_error("prefill body: head_size %d with a%s cache not supported (128, or 64 with a bf16 cache)", head_size,
+              kv8 ? "n fp8" : " bf16");
+    return AIC_ERR_UNSUPPORTED;
+  }
   AIC_REQUIRE(!kv8 || (k_scale && v_scale), "an fp8 kv cache needs k_scale and v_scale (device scalars)");
   AIC_REQUIRE(q_stride % 8 == 0 && out_stride % 8 == 0 && block_stride % 16 == 0, "strides must keep 16-byte alignment");
   if (block_size % 16 != 0) {
@@ -460,8 +540,8 @@ int aic_step_attention(const void* q, int64_t q_stride, const void* k_cache, con
               "a mixed step needs the compact decode query_start_loc and token index");
   AIC_NEED_DEVICE();
 
-  const PfGrid gr = pf_grid(n_prefill, max_prefill_q_len, num_q_heads, num_kv_heads, max_seq_len);
-  const size_t pf_bytes = pf_workspace_bytes(n_prefill, max_prefill_q_len, num_q_heads, num_kv_heads);
+  const PfGrid gr = pf_grid(n_prefill, max_prefill_q_len, num_q_heads, num_kv_heads, max_seq_len, sliding_window);
+  const size_t pf_bytes = pf_workspace_bytes(n_prefill, max_prefill_q_len, num_q_heads, num_kv_heads, head_size);
   AIC_REQUIRE(workspace_bytes >= pf_bytes, "workspace too small (%zu bytes, the prefill part needs %zu)", workspace_bytes,
               pf_bytes);
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -480,11 +560,12 @@ int aic_step_attention(const void* q, int64_t q_stride, const void* k_cache, con
                        q_stride * 2, q_dec, static_cast<int64_t>(row_bytes), decode_token_index, static_cast<int>(row_bytes), 0);
     int rc = launch_status("step_rows_kernel");
     if (rc != AIC_OK) return rc;
-    rc = aic_verify_attention_ex(q_dec, num_q_heads * head_size, k_cache, v_cache, block_stride, kv_dtype, k_scale, v_scale,
-                                 block_table, max_blocks_per_seq, seq_lens, decode_query_start_loc, batch, num_decode_tokens,
-                                 max_decode_q_len, num_q_heads, num_kv_heads, head_size, block_size, sm_scale, o_dec,
-                                 num_q_heads * head_size, dec + 2 * stage, workspace_bytes - pf_bytes - 2 * stage,
-                                 max_seq_len, short_reqs, n_short + n_prefill, long_reqs, n_long, stream);
+    rc = aic_verify_attention_win(q_dec, num_q_heads * head_size, k_cache, v_cache, block_stride, kv_dtype, k_scale,
+                                  v_scale, block_table, max_blocks_per_seq, seq_lens, decode_query_start_loc, batch,
+                                  num_decode_tokens, max_decode_q_len, num_q_heads, num_kv_heads, head_size, block_size,
+                                  sm_scale, o_dec, num_q_heads * head_size, dec + 2 * stage,
+                                  workspace_bytes - pf_bytes - 2 * stage, max_seq_len, short_reqs, n_short + n_prefill,
+                                  long_reqs, n_long, sliding_window, sinks, stream);
     if (rc != AIC_OK) return rc;
     hipLaunchKernelGGL(step_rows_kernel, dim3(num_decode_tokens), dim3(256), 0, s, static_cast<const char*>(o_dec),
                        static_cast<int64_t>(row_bytes), static_cast<char*>(out), out_stride * 2, decode_token_index,
@@ -506,7 +587,7 @@ int aic_step_attention(const void* q, int64_t q_stride, const void* k_cache, con
   P.v_scale = v_scale;
   P.out = static_cast<uint16_t*>(out);
   P.ws_o = reinterpret_cast<float*>(ws);
-  P.ws_ml = P.ws_o + static_cast<size_t>(gr.n_splits) * gr.n_wg * kPfRows * kPfD;
+  P.ws_ml = P.ws_o + static_cast<size_t>(gr.n_splits) * gr.n_wg * kPfRows * head_size;
   P.q_stride = q_stride;
   P.out_stride = out_stride;
   P.block_stride = block_stride;
@@ -520,16 +601,12 @@ int aic_step_attention(const void* q, int64_t q_stride, const void* k_cache, con
   P.n_wg = gr.n_wg;
   P.n_splits = gr.n_splits;
   P.sm_scale = sm_scale;
+  P.window = sliding_window;
+  P.sinks = sinks;
   const dim3 grid(static_cast<unsigned>(gr.n_wg) * gr.n_splits);
-  if (kv8)
-    hipLaunchKernelGGL(prefill_attn_kernel<true>, grid, dim3(256), 0, s, P);
-  else
-    hipLaunchKernelGGL(prefill_attn_kernel<false>, grid, dim3(256), 0, s, P);
-  int rc = launch_status("prefill_attn_kernel");
-  if (rc != AIC_OK || gr.n_splits == 1) return rc;
-  const int64_t rows = static_cast<int64_t>(gr.n_wg) * kPfRows;
-  hipLaunchKernelGGL(prefill_combine_kernel, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), 0, s, P);
-  return launch_status("prefill_combine_kernel");
+  if (head_size == 128)
+    return sliding_window > 0 ? launch_prefill<128, true>(P, kv8, grid, s) : launch_prefill<128, false>(P, kv8, grid, s);
+  return sliding_window > 0 ? launch_prefill<64, true>(P, kv8, grid, s) : launch_prefill<64, false>(P, kv8, grid, s);
 }
 
 }  // extern "C"

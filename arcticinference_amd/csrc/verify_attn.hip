@@ -111,16 +111,6 @@ __device__ __forceinline__ int window_begin(const AttnParams& P, int ctx, int q_
 // eight workgroups at eight different times).  !WH (Hkv not a multiple of 4, e.g. one kv head per rank under
 // SP=8, where rows are contiguous anyway): the four waves split the token range of one head and are merged
 // through LDS at the end.
-// Image of a 32-token tile for head size D: D = 128 is v_tile_off; D = 64 (128-byte rows, 8 chunks) XORs the chunk
-// with the row (the secondary head size: correct and DMA-fillable first, bank-optimal second).
-template <int D>
-__device__ __forceinline__ int tile_off(int t, int ch) {
-  if constexpr (D == 128) {
-    return v_tile_off(t, ch);
-  } else {
-    return 128 * t + 16 * (ch ^ (t & 7));
-  }
-}
 
 // maxima without the canonicalising v_max(x, x) the compiler puts in front of every fmaxf of a value it cannot prove quiet
 // (MFMA results): scores are never signalling NaNs

@@ -345,11 +345,15 @@ def step_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor
                    q_lens_host: Optional[Sequence[int]] = None, step_split: Optional[StepSplit] = None,
                    out: Optional[torch.Tensor] = None, num_splits_max: int = 64,
                    k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None,
-                   stream: Optional[int] = None) -> torch.Tensor:
-    """Attention for a whole step whatever its query lengths (aic_step_attention): prefill chunks (q_len > 33) beside
-    decodes and long drafts, in any batch order.  Same tensors and conventions as verify_attention; the step's
-    geometry comes from `q_lens_host` or a StepSplit built from it once per step (pass that to every layer)."""
-    _need_cuda(q, k_cache, v_cache, block_table, seq_lens, query_start_loc)
+                   stream: Optional[int] = None, sliding_window: int = 0,
+                   sinks: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Attention for a whole step whatever its query lengths (aic_step_attention_win): prefill chunks (q_len > 33)
+    beside decodes and long drafts, in any batch order.  Same tensors and conventions as verify_attention; the step's
+    geometry comes from `q_lens_host` or a StepSplit built from it once per step (pass that to every layer).
+    `sliding_window` W > 0 / `sinks` f32 [Hq]: the per-layer features of gpt-oss-class models, as in verify_attention."""
+    if sinks is not None and (sinks.dtype != torch.float32 or sinks.numel() != q.shape[1] or not sinks.is_contiguous()):
+        raise ValueError("sinks: contiguous float32, one value per query head")
+    _need_cuda(q, k_cache, v_cache, block_table, seq_lens, query_start_loc, sinks)
     T, Hq, D = q.shape
     nb, bs, Hkv, D2 = k_cache.shape
     assert D == D2 and q.stride(2) == 1 and q.stride(1) == D
@@ -365,13 +369,13 @@ def step_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor
     wsb = N.lib().aic_step_attention_workspace_bytes(sp.num_decode_tokens, sp.n_prefill, sp.max_prefill_q_len, Hq, Hkv, D,
                                                      num_splits_max)
     ws = _workspace(wsb, q.device, stream)
-    N.check(N.lib().aic_step_attention(
+    N.check(N.lib().aic_step_attention_win(
         q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(0),
         N.torch_dtype_code(k_cache.dtype), _ptr(k_scale), _ptr(v_scale), block_table.data_ptr(), block_table.size(1),
         seq_lens.data_ptr(), query_start_loc.data_ptr(), sp.batch, sp.num_tokens, Hq, Hkv, D, bs, float(sm_scale),
         out.data_ptr(), out.stride(0), ws.data_ptr(), ws.numel(), int(max_seq_len), sp.req_lists.data_ptr(), sp.n_short,
         sp.n_prefill, sp.n_long, sp.decode_qsl.data_ptr(), _ptr(sp.decode_index) if sp.num_decode_tokens else None,
-        sp.num_decode_tokens, max(1, sp.max_decode_q_len), sp.max_prefill_q_len,
+        sp.num_decode_tokens, max(1, sp.max_decode_q_len), sp.max_prefill_q_len, int(sliding_window or 0), _ptr(sinks),
         N.current_stream_ptr() if stream is None else stream))
     return out
 

@@ -264,9 +264,10 @@ def build_ulysses_patches():
             fp8 = kv_cache.dtype in (torch.uint8, torch.float8_e4m3fn)
             if fp8 and self.head_size != 128:
                 return None
-            # steps with prefill chunks (ARCTIC_INFERENCE_HIP_PREFILL): aic_step_attention, on layers its prefill body serves
+            # steps with prefill chunks (ARCTIC_INFERENCE_HIP_PREFILL): aic_step_attention_win, on layers its prefill body
+            # serves (head size 128, or 64 with a bf16 cache; any window, sinks or none)
             route = step_context.route(max_q, step_context.q_lens(), meta.seq_lens.numel(), step_context.prefill_on(),
-                                       self.head_size == 128 and window == 0 and sinks is None, capturing)
+                                       self.head_size == 128 or (self.head_size == 64 and not fp8), capturing)
             if route == "fallback":
                 return None
             n = meta.num_actual_tokens
@@ -291,7 +292,7 @@ def build_ulysses_patches():
                                    meta.query_start_loc.to(torch.int32), int(meta.max_seq_len), float(self.impl.scale),
                                    step_split=step_context.step_split(hq // self.num_kv_heads, query.device),
                                    out=out[:n].view(n, hq, D), k_scale=self._k_scale if fp8 else None,
-                                   v_scale=self._v_scale if fp8 else None)
+                                   v_scale=self._v_scale if fp8 else None, sliding_window=window, sinks=sinks)
                 step_context.calls["verify"] += 1
                 step_context.calls["prefill"] += 1
                 return out

@@ -448,7 +448,7 @@ int aic_verify_attention_layers(const void* q, int64_t q_stride, int64_t q_layer
  * A5p  Whole-step attention with prefill chunks — what `self._orig_forward(q_, k_, v_)` reaches through vLLM's attention
  *      backend for ANY step (ulysses.py:510): decodes, long drafts and prefill chunks (q_len > 33, chunked prefill and
  *      the Ulysses SP prefill) in one call.  Same semantics, layouts and cache dtypes as aic_verify_attention; the
- *      prefill part needs head_size 128 and at most 8 query heads per kv head.
+ *      prefill part needs head_size 128 (or 64 with a bf16 cache) and at most 8 query heads per kv head.
  *        req_lists: device int32[batch] = the short requests (n_short, q_len * Hq/Hkv <= 32 rows), then the prefill
  *            requests (n_prefill), then the long drafts (n_long); together a partition of the batch, in any order of
  *            the batch (ops.split_order3).
@@ -475,6 +475,24 @@ int aic_step_attention(const void* q, int64_t q_stride, const void* k_cache, con
                        const int32_t* req_lists, int n_short, int n_prefill, int n_long,
                        const int32_t* decode_query_start_loc, const int32_t* decode_token_index, int num_decode_tokens,
                        int max_decode_q_len, int max_prefill_q_len, void* stream);
+/* The same with the per-layer features of gpt-oss-class models, as aic_verify_attention_win takes them (on the reference
+ * path they are arguments of vLLM's Attention layer, which `self._orig_forward` reaches for every step, prefill chunks
+ * included, ulysses.py:510):
+ *   sliding_window W > 0: query position p attends keys p - W + 1 .. p only (0: the whole context);
+ *   sinks: device f32 [num_q_heads] (NULL: none), one extra soft-max logit per head, not multiplied by sm_scale.
+ * The prefill body then serves head_size 128 (bf16 or fp8 cache) or head_size 64 (bf16 cache only; AIC_ERR_UNSUPPORTED
+ * otherwise); the decode part of a mixed step goes through aic_verify_attention_win with the same window and sinks.
+ * The workspace query above is an upper bound for every window and sink setting.
+ * aic_step_attention(...) == aic_step_attention_win(..., 0, NULL, stream). */
+int aic_step_attention_win(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache, int64_t block_stride,
+                           int kv_dtype, const float* k_scale, const float* v_scale, const int32_t* block_table,
+                           int max_blocks_per_seq, const int32_t* seq_lens, const int32_t* query_start_loc, int batch,
+                           int num_tokens, int num_q_heads, int num_kv_heads, int head_size, int block_size,
+                           float sm_scale, void* out, int64_t out_stride, void* workspace, size_t workspace_bytes,
+                           int max_seq_len, const int32_t* req_lists, int n_short, int n_prefill, int n_long,
+                           const int32_t* decode_query_start_loc, const int32_t* decode_token_index,
+                           int num_decode_tokens, int max_decode_q_len, int max_prefill_q_len, int sliding_window,
+                           const float* sinks, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A12  Ulysses head/sequence repartition — the copies around the two all-to-alls of

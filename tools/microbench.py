@@ -292,21 +292,30 @@ def _prefill_case(q_lens, ctxs, Hq, Hkv, D=128, bs=16, kv8=False):
     return q, kv, bt, seq, qsl, kw
 
 
-def _visible_keys(q_lens, ctxs, decode_too=True):
-    return sum(sum(c - n + i + 1 for i in range(n)) for n, c in zip(q_lens, ctxs) if decode_too or n > 33)
+def _visible_keys(q_lens, ctxs, decode_too=True, window=0):
+    """Keys the rows see: position p sees p + 1 keys, or min(p + 1, window) with a sliding window."""
+    w = window if window > 0 else 1 << 62
+    return sum(sum(min(c - n + i + 1, w) for i in range(n)) for n, c in zip(q_lens, ctxs) if decode_too or n > 33)
 
 
-def prefill(q_lens, ctxs, Hq=32, Hkv=8, D=128, bs=16, kv8=False, label="", sdpa=False):
-    """aic_step_attention on one step: us per call and TFLOP/s with FLOPs = 4 D Hq sum(visible keys)."""
+def prefill(q_lens, ctxs, Hq=32, Hkv=8, D=128, bs=16, kv8=False, label="", sdpa=False, window=0, sinks=False):
+    """aic_step_attention_win on one step: us per call and TFLOP/s with FLOPs = 4 D Hq sum(keys inside each row's
+    window).  A window layer reads O(window) keys per row whatever the context: latency-bound, its us per call is the
+    figure to read."""
     q, kv, bt, seq, qsl, kw = _prefill_case(q_lens, ctxs, Hq, Hkv, D, bs, kv8)
     split = ops.StepSplit(q_lens, Hq // Hkv, dev)
     out = torch.empty_like(q)
+    if window:
+        kw["sliding_window"] = window
+    if sinks:
+        kw["sinks"] = torch.randn(Hq, device=dev, dtype=torch.float32)
 
     def f():
         ops.step_attention(q, kv[0], kv[1], bt, seq, qsl, max(ctxs), D ** -0.5, step_split=split, out=out, **kw)
     us = timeit(f, iters=10, warm=2)
-    fl = 4.0 * D * Hq * _visible_keys(q_lens, ctxs)
-    print(f"prefill{' fp8kv' if kv8 else ''} {label} Hq={Hq} Hkv={Hkv} bs={bs}: {us:9.1f} us  {fl / us / 1e6:7.1f} TFLOP/s")
+    fl = 4.0 * D * Hq * _visible_keys(q_lens, ctxs, window=window)
+    feat = (f" D={D}" if D != 128 else "") + (f" W={window}" if window else "") + (" sinks" if sinks else "")
+    print(f"prefill{' fp8kv' if kv8 else ''} {label} Hq={Hq} Hkv={Hkv}{feat} bs={bs}: {us:9.1f} us  {fl / us / 1e6:7.1f} TFLOP/s")
     if sdpa:   # reference point: torch SDPA on K/V gathered into contiguous tensors (single request, bf16 only)
         (n,), (c,) = q_lens, ctxs
         nblk = (c + bs - 1) // bs
@@ -334,6 +343,18 @@ def prefill_suite():
     dec = prefill(dq, dc, label="decode-only 63")
     chunk = prefill([2048], [4096], label="chunk-only 2048")
     print(f"mixed / (decode-only + chunk-only) = {mixed / (dec + chunk):.3f}")
+    # gpt-oss-120b (Hq 64, Hkv 8, head size 64; layers alternate a 128-token window and full attention, sinks on all)
+    prefill([2048], [4096], Hq=64, Hkv=8, D=64, sinks=True, label="gpt-oss chunk 2048 ctx 4096", sdpa=True)
+    for c in (4096, 16384, 32768):
+        prefill([2048], [c], Hq=64, Hkv=8, D=64, window=128, sinks=True, label=f"gpt-oss chunk 2048 ctx {c}")
+    for c in (16384, 32768):        # its SP = 8 slice: 8 query heads on one kv head per rank
+        prefill([8192], [c], Hq=8, Hkv=1, D=64, sinks=True, label=f"gpt-oss sp8 chunk 8192 ctx {c}")
+        prefill([8192], [c], Hq=8, Hkv=1, D=64, window=128, sinks=True, label=f"gpt-oss sp8 chunk 8192 ctx {c}")
+    g = dict(Hq=64, Hkv=8, D=64, window=128, sinks=True)
+    mixed = prefill(dq[:31] + [2048] + dq[31:], dc[:31] + [4096] + dc[31:], label="gpt-oss mixed 63 decodes + chunk 2048", **g)
+    dec = prefill(dq, dc, label="gpt-oss decode-only 63", **g)
+    chunk = prefill([2048], [4096], label="gpt-oss chunk-only 2048", **g)
+    print(f"gpt-oss W=128 mixed / (decode-only + chunk-only) = {mixed / (dec + chunk):.3f}")
 
 
 def lstm(B, fp8=True):
