@@ -406,6 +406,605 @@ static int dispatch(const void* logits, int dtype, int64_t row_stride, int vocab
   }
 }
 
+
+// ================================================================================================
+// Top-k / top-p rows (aic_rejection_random_topk_topp): vLLM 0.9.2's compute_probs / apply_top_k_top_p restated as a
+// radix select on the order-preserving key of x = round(l / T), never a sort.
+//
+// Launches over the grid (rows, S) — S vocab segments per row, the split of aic_rejection_random:
+//   stats   logits_row_kernel<T, 1>: per-segment (max, sum exp) partials, unchanged;
+//   K d     top-k, digit d (8 bits, most significant first): per-segment LDS count histogram of the keys whose higher
+//           digits equal the prefix chosen so far;
+//   P d     mass histogram (fixed point, 2^-40 units of exp(x - max), integer LDS atomics: order-free, deterministic)
+//           over the top-k survivors; P 0 also yields Z_k, the survivors' mass;
+//   final   p = exp(x - max) / Z_kept over kept tokens, 0 elsewhere: p[draft] and the recovered-token partials that
+//           accept_kernel<true> reads, in the workspace layout of aic_rejection_random.
+// Every launch folds the previous launch's per-segment histograms of its row in its prologue (fixed segment order) and
+// picks the next digit; per-row state and histograms are ping-ponged between launches.  Keys are 16 bits for bf16 /
+// fp16 (two digit passes) and 32 bits for f32 (four).  Rows without a filter leave the K / P launches at once and take
+// exactly the arithmetic of aic_rejection_random's mode-2 pass.
+// ================================================================================================
+template <typename T>
+struct KeyOf;
+template <>
+struct KeyOf<float> {
+  static constexpr int kBits = 32;
+  static __device__ __forceinline__ uint32_t key(float x) {
+    const uint32_t b = __float_as_uint(x);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+  }
+};
+template <>
+struct KeyOf<bf16_t> {
+  static constexpr int kBits = 16;
+  static __device__ __forceinline__ uint32_t key(float x) {  // x is bf16-exact: its low 16 bits are zero
+    const uint32_t b = __float_as_uint(x) >> 16;
+    return (b & 0x8000u) ? (~b & 0xFFFFu) : (b | 0x8000u);
+  }
+};
+template <>
+struct KeyOf<f16_t> {
+  static constexpr int kBits = 16;
+  static __device__ __forceinline__ uint32_t key(float x) {
+    const uint32_t b = f32_to_f16(x);
+    return (b & 0x8000u) ? (~b & 0xFFFFu) : (b | 0x8000u);
+  }
+};
+// value-based rules: -0 and +0 are the same value
+template <typename T>
+__device__ __forceinline__ uint32_t key_of(float x) { return KeyOf<T>::key(x == 0.0f ? 0.0f : x); }
+
+constexpr float kMassScale = 1099511627776.0f;  // 2^40: fixed-point unit of the mass histograms
+constexpr double kMassUnit = 1.0 / 1099511627776.0;
+typedef unsigned long long u64;
+
+__device__ __forceinline__ u64 fixed_mass(float e) { return static_cast<u64>(e * kMassScale); }
+
+enum { kPassStats = -1, kPassK = 0, kPassP = 1, kPassFinal = 2 };
+
+struct TopState {
+  u64 krem;      // top-k: k minus the tokens above the prefix's range
+  u64 prem;      // top-p: T minus the mass below the prefix's range
+  u64 zk;        // mass of the top-k survivors
+  u64 thr;       // T = floor((1 - p) * zk)
+  float m;       // row max of x
+  uint32_t kprefix, pprefix, pad;
+};
+
+struct TopkArgs {
+  const void* logits;
+  int64_t row_stride;
+  const int32_t* draft;
+  const int32_t* cu;
+  const float* temperature;
+  const float* exp_noise;
+  const int32_t* top_k;
+  const float* top_p;
+  const int64_t* row_index;
+  float* part_val;
+  int32_t* part_idx;
+  const float* stat_max;
+  const float* stat_sum;
+  float* p_draft;
+  TopState* state;  // [2][rows]
+  uint32_t* cnt;    // [2][rows][n_splits][256]
+  u64* mass;        // [2][rows][n_splits][256]
+  int batch, rows, vocab, seg_len, n_splits;
+  int launch;       // 0 for the first launch after the stats pass: ping-pong parity
+  int digit;        // digit of this K / P pass
+  int prev_pass, prev_digit;
+};
+
+struct RowFilter {
+  int req;
+  float temp;
+  bool greedy, fk, fp;
+  int k;
+  float p;
+};
+
+__device__ __forceinline__ RowFilter row_filter(const TopkArgs& a, int row) {
+  RowFilter f;
+  f.req = request_of_row(a.cu, a.batch, row);
+  f.temp = a.temperature[f.req];
+  f.greedy = !(f.temp > 0.0f);
+  f.k = a.top_k ? a.top_k[f.req] : 0;
+  f.p = a.top_p ? a.top_p[f.req] : 1.0f;
+  f.fk = !f.greedy && f.k > 0 && f.k < a.vocab;  // k <= 0 or k >= vocab: no top-k
+  f.fp = !f.greedy && f.p < 1.0f;                // p >= 1: no top-p
+  return f;
+}
+
+// Visits the elements of [begin, end) of a row (thread-strided, 16-byte loads when VEC_OK).
+template <typename T, bool VEC_OK, typename F>
+__device__ __forceinline__ void for_each_elem(const T* base, int begin, int end, F&& f) {
+  constexpr int V = Elem<T>::kVec;
+  if (VEC_OK) {
+    for (int i = begin + threadIdx.x * V; i < end; i += 256 * V) {
+      if (i + V <= end) {
+        T buf[V];
+        *reinterpret_cast<uint4*>(buf) = *reinterpret_cast<const uint4*>(base + i);
+#pragma unroll
+        for (int e = 0; e < V; ++e) f(i + e, Elem<T>::get(buf, e));
+      } else {
+        for (int e = 0; i + e < end; ++e) f(i + e, Elem<T>::get(base + i, e));
+      }
+    }
+  } else {
+    for (int i = begin + threadIdx.x; i < end; i += 256) f(i, Elem<T>::get(base + i, 0));
+  }
+}
+
+// Sum of the previous launch's per-segment histograms of `row`, in segment order: s_c / s_m [256].
+__device__ void fold_hist(const TopkArgs& a, int row, bool want_mass, u64* s_c, u64* s_m) {
+  const size_t base = (static_cast<size_t>((a.launch - 1) & 1) * a.rows + row) * a.n_splits * 256 + threadIdx.x;
+  u64 c = 0, m = 0;
+  for (int s = 0; s < a.n_splits; ++s) {
+    c += a.cnt[base + static_cast<size_t>(s) * 256];
+    if (want_mass) m += a.mass[base + static_cast<size_t>(s) * 256];
+  }
+  s_c[threadIdx.x] = c;
+  s_m[threadIdx.x] = m;
+}
+
+// Wave 0: the first bin (ascending bins if `asc`, else descending) at which the running sum of s_val exceeds `target`,
+// the sum before it (the last bin if the sum never does) and the total; the same answer in every lane.
+struct Sel {
+  int bin;
+  u64 before, total;
+};
+__device__ Sel select_bin(const u64* s_val, bool asc, u64 target) {
+  const int lane = threadIdx.x;
+  u64 v[4], sum = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int j = lane * 4 + i;
+    v[i] = s_val[asc ? j : 255 - j];
+    sum += v[i];
+  }
+  u64 incl = sum;
+  for (int off = 1; off < 64; off <<= 1) {
+    const u64 t = __shfl_up(incl, off);
+    if (lane >= off) incl += t;
+  }
+  const unsigned long long hit = __ballot(incl > target);
+  const int L = hit ? (__ffsll(static_cast<long long>(hit)) - 1) : 63;
+  u64 cum = incl - sum;
+  int i = 0;
+  for (; i < 3; ++i) {
+    if (cum + v[i] > target) break;
+    cum += v[i];
+  }
+  const int j = lane * 4 + i;
+  Sel r;
+  r.bin = __shfl(asc ? j : 255 - j, L);
+  r.before = __shfl(cum, L);
+  r.total = __shfl(incl, 63);
+  return r;
+}
+
+__device__ __forceinline__ int digit_shift(int bits, int d) { return bits - 8 * (d + 1); }
+__device__ __forceinline__ bool prefix_match(uint32_t key, uint32_t prefix, int bits, int d) {
+  return d == 0 || (key >> (bits - 8 * d)) == (prefix >> (bits - 8 * d));
+}
+
+// Block-wide exclusive prefix sum of `c` in thread order; `total` gets the block's sum.
+__device__ __forceinline__ int block_excl_scan(int c, int* s_w, int* total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int incl = c;
+  for (int off = 1; off < 64; off <<= 1) {
+    const int t = __shfl_up(incl, off);
+    if (lane >= off) incl += t;
+  }
+  if (lane == 63) s_w[wave] = incl;
+  __syncthreads();
+  int before = 0;
+  for (int w = 0; w < wave; ++w) before += s_w[w];
+  *total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+  __syncthreads();
+  return before + incl - c;
+}
+
+
+template <typename T, int PASS, bool VEC_OK>
+__global__ void __launch_bounds__(256) topk_row_kernel(TopkArgs a) {
+  constexpr int BITS = KeyOf<T>::kBits;
+  const int row = blockIdx.x;
+  const int seg = blockIdx.y;
+  const int tid = threadIdx.x;
+  const int begin = seg * a.seg_len;
+  const int end = min(begin + a.seg_len, a.vocab);
+  const RowFilter f = row_filter(a, row);
+  const bool filtered = f.fk || f.fp;
+  if (PASS != kPassFinal && !filtered) return;  // unfiltered and greedy rows only take the final pass
+  const T* base = static_cast<const T*>(a.logits) + (a.row_index ? a.row_index[row] : static_cast<int64_t>(row)) * a.row_stride;
+
+  __shared__ u64 s_c[256], s_m[256];  // folded histograms of the previous launch
+  __shared__ uint32_t s_hc[256];      // this block's histograms
+  __shared__ u64 s_hm[256];
+  __shared__ TopState s_st;
+  __shared__ float s_rmax, s_rz, s_zf;
+  __shared__ uint32_t s_tau_p;
+  __shared__ int s_dlocal, s_ties_here;
+  __shared__ int s_w[4];
+  __shared__ float s_v[4];
+  __shared__ int s_i[4];
+
+  // ---- the row's softmax statistics, folded exactly as the mode-2 pass of aic_rejection_random folds them
+  float row_max = 0.0f, row_z = 1.0f;
+  if (!f.greedy) {
+    if (tid < 64) {
+      float m = -INFINITY;
+      for (int s = tid; s < a.n_splits; s += 64) m = fmaxf(m, a.stat_max[row * a.n_splits + s]);
+      m = wave_max(m);
+      float z = 0.0f;
+      for (int s = tid; s < a.n_splits; s += 64) {
+        const float pm = a.stat_max[row * a.n_splits + s];
+        if (pm > -INFINITY) z += a.stat_sum[row * a.n_splits + s] * __expf(pm - m);
+      }
+      z = wave_sum(z);
+      if (tid == 0) {
+        s_rmax = m;
+        s_rz = z;
+      }
+    }
+    __syncthreads();
+    row_max = s_rmax;
+    row_z = s_rz;
+  }
+
+  // ---- fold the previous launch's histograms into the row's selection state
+  if (filtered) {
+    if (tid == 0) {
+      TopState st;
+      if (a.launch == 0) {
+        st.krem = static_cast<u64>(f.fk ? f.k : 0);
+        st.prem = st.zk = st.thr = 0;
+        st.kprefix = st.pprefix = st.pad = 0;
+      } else {
+        st = a.state[static_cast<size_t>((a.launch - 1) & 1) * a.rows + row];
+      }
+      s_st = st;
+    }
+    const bool fold_k = a.prev_pass == kPassK && f.fk;
+    const bool fold_p = a.prev_pass == kPassP && (a.prev_digit == 0 || f.fp);
+    if (fold_k || fold_p) fold_hist(a, row, fold_p, s_c, s_m);
+    __syncthreads();
+    if (tid < 64 && (fold_k || fold_p)) {
+      TopState st = s_st;
+      if (fold_k) {  // the bin of the k-th largest key, counting from the top
+        const Sel s = select_bin(s_c, false, st.krem - 1);
+        st.kprefix |= static_cast<uint32_t>(s.bin) << digit_shift(BITS, a.prev_digit);
+        st.krem -= s.before;
+      } else {
+        if (a.prev_digit == 0) {  // Z_k and T = (1 - p) Z_k
+          st.zk = select_bin(s_m, true, ~0ull).total;
+          if (f.fp) {
+            st.thr = f.p > 0.0f ? static_cast<u64>(static_cast<double>(st.zk) * (1.0 - static_cast<double>(f.p)))
+                                : st.zk - 1;  // p <= 0: only the largest survivor stays
+            st.prem = st.thr;
+          }
+        }
+        if (f.fp) {  // the first bin, counting from the bottom, whose cumulative mass exceeds T
+          const Sel s = select_bin(s_m, true, st.prem);
+          st.pprefix |= static_cast<uint32_t>(s.bin) << digit_shift(BITS, a.prev_digit);
+          st.prem -= s.before;
+          if (PASS == kPassFinal && tid == 0) {
+            // boundary value tau_p: its n ties carry qe each; the lowest d of them (index order) are dropped, d the
+            // number of j in 1..n with L + j qe <= T (prem = T - L); the largest survivor always stays
+            const u64 n = s_c[s.bin];
+            const u64 qe = n ? s_m[s.bin] / n : 0;
+            u64 d = qe ? st.prem / qe : 0;
+            if (d > n) d = n;
+            if (st.pprefix == key_of<T>(row_max) && d >= n) d = n ? n - 1 : 0;
+            const u64 zkept = st.zk - (st.thr - st.prem) - d * qe;
+            s_zf = static_cast<float>(static_cast<double>(zkept) * kMassUnit);
+            s_tau_p = st.pprefix;
+            const size_t hb = (static_cast<size_t>((a.launch - 1) & 1) * a.rows + row) * a.n_splits * 256 + (st.pprefix & 0xFF);
+            u64 before = 0;
+            for (int s2 = 0; s2 < seg; ++s2) before += a.cnt[hb + static_cast<size_t>(s2) * 256];
+            s_ties_here = static_cast<int>(a.cnt[hb + static_cast<size_t>(seg) * 256]);
+            s_dlocal = d > before ? static_cast<int>(d - before) : 0;
+          }
+        }
+      }
+      if (tid == 0) s_st = st;
+    }
+    if (PASS == kPassFinal && tid == 0 && !f.fp) {
+      s_zf = static_cast<float>(static_cast<double>(s_st.zk) * kMassUnit);
+      s_tau_p = 0;
+      s_dlocal = 0;
+      s_ties_here = 0;
+    }
+    __syncthreads();
+    if (PASS != kPassFinal && seg == 0 && tid == 0) a.state[static_cast<size_t>(a.launch & 1) * a.rows + row] = s_st;
+  }
+
+  if (PASS != kPassFinal) {
+    if (PASS == kPassK ? !f.fk : (a.digit > 0 && !f.fp)) return;
+    const TopState st = s_st;
+    const int d = a.digit;
+    const int sh = digit_shift(BITS, d);
+    const uint32_t prefix = PASS == kPassK ? st.kprefix : st.pprefix;
+    const bool cut_k = PASS == kPassP && f.fk;
+    s_hc[tid] = 0;
+    s_hm[tid] = 0;
+    __syncthreads();
+    // runs of equal bins are added to LDS once (the high digits of a row's keys take few values)
+    int cur = -1;
+    uint32_t cc = 0;
+    u64 cm = 0;
+    auto flush = [&]() {
+      if (cur >= 0) {
+        atomicAdd(&s_hc[cur], cc);
+        if (PASS == kPassP) atomicAdd(&s_hm[cur], cm);
+      }
+    };
+    for_each_elem<T, VEC_OK>(base, begin, end, [&](int idx, float l) {
+      (void)idx;
+      const float x = Elem<T>::round(__fdiv_rn(l, f.temp));
+      const uint32_t key = key_of<T>(x);
+      if (!prefix_match(key, prefix, BITS, d)) return;
+      u64 q = 0;
+      if (PASS == kPassP) {
+        if (cut_k && key < st.kprefix) return;
+        q = fixed_mass(__expf(x - row_max));
+        if (q == 0) return;  // no mass: below any top-p boundary, nothing to add to Z_k
+      }
+      const int b = (key >> sh) & 0xFF;
+      if (b != cur) {
+        flush();
+        cur = b;
+        cc = 0;
+        cm = 0;
+      }
+      ++cc;
+      cm += q;
+    });
+    flush();
+    __syncthreads();
+    const size_t o = (static_cast<size_t>(a.launch & 1) * a.rows + row) * a.n_splits * 256 + static_cast<size_t>(seg) * 256 + tid;
+    a.cnt[o] = s_hc[tid];
+    if (PASS == kPassP) a.mass[o] = s_hm[tid];
+    return;
+  }
+
+  // ---- final pass: p over the kept set, p[draft], recovered-token partials
+  const int draft = a.draft[row];
+  const float* q = a.exp_noise + static_cast<int64_t>(f.req) * a.vocab;
+  const uint32_t tau_k = s_st.kprefix, tau_p = s_tau_p;
+  const float zf = s_zf;
+  const int dlocal = s_dlocal, ties_here = s_ties_here;
+  Best best;
+  best.v = -INFINITY;
+  best.i = begin;
+  auto visit = [&](int idx, float l, bool tie_keep) {
+    if (f.greedy) {
+      if (l > best.v) {
+        best.v = l;
+        best.i = idx;
+      }
+      return;
+    }
+    const float x = Elem<T>::round(__fdiv_rn(l, f.temp));
+    float p;
+    if (!filtered) {
+      p = __fdiv_rn(__expf(x - row_max), row_z);
+    } else {
+      const uint32_t key = key_of<T>(x);
+      const bool kept = (!f.fk || key >= tau_k) && (!f.fp || key > tau_p || (key == tau_p && tie_keep));
+      p = kept ? __fdiv_rn(__expf(x - row_max), zf) : 0.0f;
+    }
+    if (idx == draft) {
+      a.p_draft[row] = p;
+      p = 0.0f;
+    }
+    const float r = __fdiv_rn(p, q[idx]);
+    if (r > best.v) {
+      best.v = r;
+      best.i = idx;
+    }
+  };
+  if (f.fp && dlocal > 0 && dlocal < ties_here) {
+    // the cut falls inside this segment's ties: rank them in index order (8 contiguous elements per thread)
+    const int n_iter = (end - begin + 2047) / 2048;
+    int seen = 0;
+    for (int it = 0; it < n_iter; ++it) {
+      const int i0 = begin + it * 2048 + tid * 8;
+      float lv[8];
+      int c = 0;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        lv[e] = i0 + e < end ? Elem<T>::get(base, i0 + e) : 0.0f;
+        if (i0 + e < end && key_of<T>(Elem<T>::round(__fdiv_rn(lv[e], f.temp))) == tau_p) ++c;
+      }
+      int total;
+      int rank = seen + block_excl_scan(c, s_w, &total);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        if (i0 + e >= end) continue;
+        const bool tie = key_of<T>(Elem<T>::round(__fdiv_rn(lv[e], f.temp))) == tau_p;
+        visit(i0 + e, lv[e], !tie || rank >= dlocal);
+        rank += tie;
+      }
+      seen += total;
+    }
+  } else {
+    const bool keep_ties = dlocal <= 0;  // 0 < ties_here <= dlocal: every tie of this segment is dropped
+    for_each_elem<T, VEC_OK>(base, begin, end, [&](int idx, float l) { visit(idx, l, keep_ties); });
+  }
+
+  const int wave = tid >> 6, lane = tid & 63;
+  best = wave_best(best);
+  if (lane == 0) {
+    s_v[wave] = best.v;
+    s_i[wave] = best.i;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    Best b;
+    b.v = s_v[0];
+    b.i = s_i[0];
+    for (int w = 1; w < 4; ++w) {
+      Best o;
+      o.v = s_v[w];
+      o.i = s_i[w];
+      b = better(b, o);
+    }
+    a.part_val[row * a.n_splits + seg] = b.v;
+    a.part_idx[row * a.n_splits + seg] = b.i;
+  }
+}
+
+static void split_geometry(int rows, int vocab, int* seg_len, int* n_splits) {
+  const int S = rows > 0 ? pick_splits(rows, vocab) : 1;
+  int len = (vocab + S - 1) / S;
+  len = (len + kSegQuantum - 1) / kSegQuantum * kSegQuantum;
+  *seg_len = len;
+  *n_splits = (vocab + len - 1) / len;
+}
+
+static size_t topk_region_offset(int rows, int vocab);
+
+template <typename T>
+static int run_rejection_topk(const void* logits, int64_t row_stride, int vocab, const int32_t* draft,
+                              const int32_t* cu, const int32_t* bonus, const float* temperature, const double* uniform,
+                              const float* noise, const int32_t* top_k, const float* top_p, int batch, int rows,
+                              int max_spec_len, int32_t* out, int32_t* nacc, int32_t* last, int32_t* hidx,
+                              const int64_t* row_index, void* workspace, hipStream_t stream) {
+  int seg_len, n_splits;
+  split_geometry(rows, vocab, &seg_len, &n_splits);
+  // the layout of aic_rejection_random (accept_kernel<true> reads it unchanged), then the selection state
+  float* part_val = static_cast<float*>(workspace);
+  const size_t wr = static_cast<size_t>(rows);
+  int32_t* part_idx = reinterpret_cast<int32_t*>(part_val + wr * kMaxSplits);
+  float* stat_max = reinterpret_cast<float*>(part_idx + wr * kMaxSplits);
+  float* stat_sum = stat_max + wr * kMaxSplits;
+  float* p_draft = stat_sum + wr * kMaxSplits;
+  TopState* state = reinterpret_cast<TopState*>(static_cast<char*>(workspace) + topk_region_offset(rows, vocab));
+  uint32_t* cnt = reinterpret_cast<uint32_t*>(state + 2 * wr);
+  u64* mass = reinterpret_cast<u64*>(cnt + 2 * wr * n_splits * 256);
+  const T* lg = static_cast<const T*>(logits);
+  const bool vec_ok = (reinterpret_cast<uintptr_t>(logits) % 16 == 0) && ((row_stride * sizeof(T)) % 16 == 0);
+  if (rows > 0) {
+    dim3 grid(rows, n_splits);
+    if (vec_ok)
+      hipLaunchKernelGGL((logits_row_kernel<T, 1, true>), grid, dim3(256), 0, stream, lg, row_stride, vocab, seg_len,
+                         n_splits, draft, cu, batch, temperature, noise, part_val, part_idx, stat_max, stat_sum,
+                         p_draft, row_index, nullptr, rows);
+    else
+      hipLaunchKernelGGL((logits_row_kernel<T, 1, false>), grid, dim3(256), 0, stream, lg, row_stride, vocab, seg_len,
+                         n_splits, draft, cu, batch, temperature, noise, part_val, part_idx, stat_max, stat_sum,
+                         p_draft, row_index, nullptr, rows);
+    int rc = launch_status("logits_row_kernel<stats>");
+    if (rc != AIC_OK) return rc;
+    TopkArgs a;
+    a.logits = logits;
+    a.row_stride = row_stride;
+    a.draft = draft;
+    a.cu = cu;
+    a.temperature = temperature;
+    a.exp_noise = noise;
+    a.top_k = top_k;
+    a.top_p = top_p;
+    a.row_index = row_index;
+    a.part_val = part_val;
+    a.part_idx = part_idx;
+    a.stat_max = stat_max;
+    a.stat_sum = stat_sum;
+    a.p_draft = p_draft;
+    a.state = state;
+    a.cnt = cnt;
+    a.mass = mass;
+    a.batch = batch;
+    a.rows = rows;
+    a.vocab = vocab;
+    a.seg_len = seg_len;
+    a.n_splits = n_splits;
+    a.launch = 0;
+    a.digit = 0;
+    a.prev_pass = kPassStats;
+    a.prev_digit = 0;
+    auto go = [&](int pass, int digit) -> int {
+      a.digit = digit;
+#define AIC_TOPK_LAUNCH(P)                                                                                       \
+  if (vec_ok)                                                                                                    \
+    hipLaunchKernelGGL((topk_row_kernel<T, P, true>), grid, dim3(256), 0, stream, a);                           \
+  else                                                                                                           \
+    hipLaunchKernelGGL((topk_row_kernel<T, P, false>), grid, dim3(256), 0, stream, a);
+      if (pass == kPassK) {
+        AIC_TOPK_LAUNCH(kPassK)
+      } else if (pass == kPassP) {
+        AIC_TOPK_LAUNCH(kPassP)
+      } else {
+        AIC_TOPK_LAUNCH(kPassFinal)
+      }
+#undef AIC_TOPK_LAUNCH
+      a.prev_pass = pass;
+      a.prev_digit = digit;
+      ++a.launch;
+      return launch_status("topk_row_kernel");
+    };
+    constexpr int digits = KeyOf<T>::kBits / 8;
+    if (top_k)
+      for (int d = 0; d < digits && rc == AIC_OK; ++d) rc = go(kPassK, d);
+    if (rc == AIC_OK) rc = go(kPassP, 0);  // Z_k (and the first top-p digit)
+    if (top_p)
+      for (int d = 1; d < digits && rc == AIC_OK; ++d) rc = go(kPassP, d);
+    if (rc == AIC_OK) rc = go(kPassFinal, 0);
+    if (rc != AIC_OK) return rc;
+  }
+  hipLaunchKernelGGL((accept_kernel<true>), dim3(batch), dim3(64), 0, stream, part_val, part_idx, n_splits, draft, cu,
+                     bonus, temperature, uniform, p_draft, max_spec_len, out, nacc, last, hidx, -1);
+  return launch_status("accept_kernel");
+}
+
+static size_t topk_region_offset(int rows, int vocab) {
+  const size_t r = static_cast<size_t>(rows > 0 ? rows : 1);
+  const size_t base = r * kMaxSplits * 4 * sizeof(float) + r * sizeof(float) + 256;  // aic_rejection_workspace_bytes
+  (void)vocab;
+  return (base + 255) / 256 * 256;
+}
+
+static size_t topk_workspace_bytes(int rows, int vocab) {
+  int seg_len, n_splits;
+  split_geometry(rows, vocab, &seg_len, &n_splits);
+  const size_t r = static_cast<size_t>(rows > 0 ? rows : 1);
+  return topk_region_offset(rows, vocab) + 2 * r * sizeof(TopState) +
+         2 * r * static_cast<size_t>(n_splits) * 256 * (sizeof(uint32_t) + sizeof(u64)) + 256;
+}
+
+static int dispatch_topk(const void* logits, int dtype, int64_t row_stride, int vocab, const int32_t* draft,
+                         const int32_t* cu, const int32_t* bonus, const float* temperature, const double* uniform,
+                         const float* noise, const int32_t* top_k, const float* top_p, int batch, int rows,
+                         int max_spec_len, int32_t* out, int32_t* nacc, int32_t* last, int32_t* hidx,
+                         const int64_t* row_index, void* ws, void* stream) {
+  if (!top_k && !top_p)  // no filter anywhere: aic_rejection_random itself
+    return dispatch(logits, dtype, row_stride, vocab, draft, cu, bonus, temperature, uniform, noise, batch, rows,
+                    max_spec_len, out, nacc, last, hidx, row_index, nullptr, ws, stream, true);
+  if (batch == 0) return AIC_OK;
+  AIC_REQUIRE(cu && bonus && out && batch > 0 && rows >= 0 && vocab > 0, "bad arguments to rejection");
+  AIC_REQUIRE(rows == 0 || (logits && draft && ws), "null logits / draft ids / workspace");
+  AIC_REQUIRE(max_spec_len >= 0 && max_spec_len + 1 <= 64, "max_spec_len must be <= 63 (one lane per position)");
+  AIC_REQUIRE(temperature && uniform && noise, "random rejection needs temperature, uniform and noise");
+  AIC_NEED_DEVICE();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (dtype) {
+    case AIC_DT_F32:
+      return run_rejection_topk<float>(logits, row_stride, vocab, draft, cu, bonus, temperature, uniform, noise, top_k,
+                                       top_p, batch, rows, max_spec_len, out, nacc, last, hidx, row_index, ws, s);
+    case AIC_DT_BF16:
+      return run_rejection_topk<bf16_t>(logits, row_stride, vocab, draft, cu, bonus, temperature, uniform, noise, top_k,
+                                        top_p, batch, rows, max_spec_len, out, nacc, last, hidx, row_index, ws, s);
+    case AIC_DT_F16:
+      return run_rejection_topk<f16_t>(logits, row_stride, vocab, draft, cu, bonus, temperature, uniform, noise, top_k,
+                                       top_p, batch, rows, max_spec_len, out, nacc, last, hidx, row_index, ws, s);
+    default:
+      set_error("unsupported logits dtype %d", dtype);
+      return AIC_ERR_UNSUPPORTED;
+  }
+}
+
 }  // namespace aic
 
 using namespace aic;
@@ -438,6 +1037,23 @@ int aic_rejection_random(const void* target_logits, int logits_dtype, int64_t ro
   return dispatch(target_logits, logits_dtype, row_stride, vocab, draft_token_ids, cu_num_draft, bonus_token_ids,
                   temperature, uniform, exp_noise, batch, num_draft_total, max_spec_len, out_token_ids, num_accepted,
                   last_token, hidden_index, target_row_index, nullptr, workspace, stream, true);
+}
+
+size_t aic_rejection_topk_topp_workspace_bytes(int num_draft_total, int vocab, int logits_dtype) {
+  (void)logits_dtype;  // the key width changes the number of passes, not the state
+  return topk_workspace_bytes(num_draft_total, vocab > 0 ? vocab : 1);
+}
+
+int aic_rejection_random_topk_topp(const void* target_logits, int logits_dtype, int64_t row_stride, int vocab,
+                                   const int32_t* draft_token_ids, const int32_t* cu_num_draft,
+                                   const int32_t* bonus_token_ids, const float* temperature, const double* uniform,
+                                   const float* exp_noise, const int32_t* top_k, const float* top_p, int batch,
+                                   int num_draft_total, int max_spec_len, int32_t* out_token_ids, int32_t* num_accepted,
+                                   int32_t* last_token, int32_t* hidden_index, const int64_t* target_row_index,
+                                   void* workspace, void* stream) {
+  return dispatch_topk(target_logits, logits_dtype, row_stride, vocab, draft_token_ids, cu_num_draft, bonus_token_ids,
+                       temperature, uniform, exp_noise, top_k, top_p, batch, num_draft_total, max_spec_len,
+                       out_token_ids, num_accepted, last_token, hidden_index, target_row_index, workspace, stream);
 }
 
 }  // extern "C"

@@ -123,14 +123,21 @@ def rejection_sample(target_logits: torch.Tensor, draft_token_ids: torch.Tensor,
                      bonus_token_ids: torch.Tensor, max_spec_len: int, temperature: Optional[torch.Tensor] = None,
                      uniform_probs: Optional[torch.Tensor] = None, exp_noise: Optional[torch.Tensor] = None,
                      target_row_index: Optional[torch.Tensor] = None,
-                     bonus_row_index: Optional[torch.Tensor] = None) -> RejectionResult:
+                     bonus_row_index: Optional[torch.Tensor] = None, *, top_k: Optional[torch.Tensor] = None,
+                     top_p: Optional[torch.Tensor] = None) -> RejectionResult:
     """out[B, max_spec_len+1] int32 (-1 padded) as vLLM's RejectionSampler returns it for
     draft_probs=None (call site model_runner.py:405-411), plus the proposer inputs of the next step.
     `target_row_index` (int64 [num_draft_total]): pass the model's full [T, V] logits as `target_logits` and the
     rows to read (SpecDecodeMetadata.target_logits_indices) instead of a gathered copy.  `bonus_row_index` (int64 [B],
     greedy only): the bonus tokens are the arg-max of those rows of `target_logits`, computed in the same launch
-    (`bonus_token_ids` may then be None)."""
-    _need_cuda(target_logits, draft_token_ids, cu_num_draft_tokens, bonus_token_ids, target_row_index, bonus_row_index)
+    (`bonus_token_ids` may then be None).
+    `top_k` (int [B]) / `top_p` (float [B]), with `temperature` only: the random rows' probabilities are vLLM's
+    compute_probs after apply_top_k_top_p (aic_rejection_random_topk_topp: k <= 0 or k >= vocab, p >= 1 disable a
+    filter for that request)."""
+    if (top_k is not None or top_p is not None) and temperature is None:
+        raise ValueError("top_k / top_p apply to random rows: they need temperature")
+    _need_cuda(target_logits, draft_token_ids, cu_num_draft_tokens, bonus_token_ids, target_row_index, bonus_row_index,
+               top_k, top_p)
     if bonus_row_index is not None and (temperature is not None or bonus_row_index.dtype != torch.int64 or
                                         bonus_row_index.numel() != cu_num_draft_tokens.numel()):
         raise ValueError("bonus_row_index: int64, one row per request, greedy acceptance only")
@@ -160,6 +167,17 @@ def rejection_sample(target_logits: torch.Tensor, draft_token_ids: torch.Tensor,
                                              cu.data_ptr(), _ptr(bonus), B, rows, max_spec_len, out.data_ptr(),
                                              nacc.data_ptr(), last.data_ptr(), hidx.data_ptr(), _ptr(target_row_index),
                                              _ptr(bonus_row_index), ws.data_ptr(), N.current_stream_ptr()))
+    elif top_k is not None or top_p is not None:
+        tk = None if top_k is None else top_k.reshape(-1).to(torch.int32)
+        tp = None if top_p is None else top_p.reshape(-1).float()
+        if (tk is not None and tk.numel() != B) or (tp is not None and tp.numel() != B):
+            raise ValueError("top_k / top_p: one value per request")
+        ws = _workspace(N.lib().aic_rejection_topk_topp_workspace_bytes(rows, V, dt), dev, purpose="accept")
+        N.check(N.lib().aic_rejection_random_topk_topp(
+            _ptr(target_logits) if rows else None, dt, stride, V, draft.data_ptr(), cu.data_ptr(), bonus.data_ptr(),
+            temperature.float().data_ptr(), uniform_probs.double().data_ptr(), exp_noise.float().data_ptr(), _ptr(tk),
+            _ptr(tp), B, rows, max_spec_len, out.data_ptr(), nacc.data_ptr(), last.data_ptr(), hidx.data_ptr(),
+            _ptr(target_row_index), ws.data_ptr(), N.current_stream_ptr()))
     else:
         N.check(N.lib().aic_rejection_random(_ptr(target_logits) if rows else None, dt, stride, V, draft.data_ptr(),
                                              cu.data_ptr(), bonus.data_ptr(), temperature.float().data_ptr(),

@@ -31,8 +31,9 @@ import numpy as np
 import torch
 
 from . import step_context
-from .runner_logic import (INDEXING_REFERENCE, MAX_SPEC_LEN, arctic_max_spec_tokens, hip_acceptance_kind, merge_proposals,
-                           min_suffix_score, proposal_end_index, proposal_indexing, rewrite_sampled, suffix_query)
+from .runner_logic import (INDEXING_REFERENCE, KIND_TOP_K_TOP_P, MAX_SPEC_LEN, arctic_max_spec_tokens, hip_acceptance_kind,
+                           merge_proposals, min_suffix_score, proposal_end_index, proposal_indexing, rewrite_sampled,
+                           suffix_query, top_k_top_p_switch)
 
 logger = logging.getLogger(__name__)
 
@@ -480,15 +481,17 @@ def build_model_runner_patch():
               * batches with random rows (temperature only; greedy rows may be mixed in): the bonus tokens come from
                 vLLM's sampler as in the reference (:394-399), then the uniforms and the Exp(1) recovery noise are drawn
                 exactly as vLLM's rejection sampler draws them — same calls, same order, per-request generators — and
-                aic_rejection_random accepts.
-            Anything else (top-k / top-p / min-p, penalties, bias, min_tokens, masks, logprobs: runner_logic.
-            hip_acceptance_kind) keeps vLLM's sampler + RejectionSampler."""
+                aic_rejection_random accepts;
+              * with ARCTIC_INFERENCE_HIP_TOP_K_TOP_P=1 (read once per step), batches whose rows also carry top-k /
+                top-p take the same route through aic_rejection_random_topk_topp (the bonus tokens stay vLLM's sampler's).
+            Anything else (min-p, penalties, bias, min_tokens, masks, logprobs, and top-k / top-p with the switch off:
+            runner_logic.hip_acceptance_kind) keeps vLLM's sampler + RejectionSampler."""
             if spec_decode_metadata is None:
                 return self.sampler(logits=logits, sampling_metadata=sampling_metadata)
             assert logits is not None
             md = spec_decode_metadata
             sm = sampling_metadata
-            kind = hip_acceptance_kind(sm) if logits.is_cuda else None
+            kind = hip_acceptance_kind(sm, top_k_top_p_switch()) if logits.is_cuda else None
             if kind == "greedy":
                 from vllm.v1.outputs import SamplerOutput
                 max_spec = max(int(max(md.num_draft_tokens)), 1)
@@ -501,14 +504,15 @@ def build_model_runner_patch():
             # indexing with a tensor copies: in-place edits of the sampler do not reach `logits`
             bonus_logits = logits[md.bonus_logits_indices]
             out = self.sampler(logits=bonus_logits, sampling_metadata=sampling_metadata)
-            if kind == "random":
+            if kind in ("random", KIND_TOP_K_TOP_P):
+                filters = dict(top_k=sm.top_k, top_p=sm.top_p) if kind == KIND_TOP_K_TOP_P else {}
                 n_draft = md.num_draft_tokens
                 max_spec = max(int(max(n_draft)), 1)
                 uniform = draw_uniform_probs(int(md.draft_token_ids.numel()), n_draft, sm.generators, logits.device)
                 noise = draw_recovery_noise(len(n_draft), logits.shape[-1], n_draft, sm.generators, logits.device)
                 rej = ops.rejection_sample(logits, md.draft_token_ids, md.cu_num_draft_tokens, out.sampled_token_ids, max_spec,
                                            temperature=sm.temperature, uniform_probs=uniform, exp_noise=noise,
-                                           target_row_index=md.target_logits_indices.to(torch.int64))
+                                           target_row_index=md.target_logits_indices.to(torch.int64), **filters)
                 self._arctic_rej = rej
                 self._arctic_maybe_draft_early(rej, sample_hidden_states, n_draft)
                 out.sampled_token_ids = rej.output_token_ids

@@ -104,11 +104,20 @@ def arctic_max_spec_tokens(num_speculative_tokens: int, end_indices: Sequence[in
     return m
 
 
-def hip_acceptance_kind(sm) -> Optional[str]:
+TOP_K_TOP_P_ENV = "ARCTIC_INFERENCE_HIP_TOP_K_TOP_P"   # 1: top-k / top-p batches on the HIP acceptance too (default off)
+KIND_TOP_K_TOP_P = "random_topk_topp"
+
+
+def top_k_top_p_switch() -> bool:
+    return os.environ.get(TOP_K_TOP_P_ENV, "0").strip().lower() in ("1", "true", "yes", "on")
+
+
+def hip_acceptance_kind(sm, top_k_top_p: bool = False) -> Optional[str]:
     """Which acceptance kernel serves a verify step with this vLLM SamplingMetadata: "greedy" (aic_rejection_greedy),
-    "random" (aic_rejection_random: temperature-only rows, greedy rows mixed in) or None (vLLM's sampler +
-    RejectionSampler: top-k / top-p / min-p, penalties, logit bias, min_tokens, bad words, allowed-token masks and
-    logprobs live there).  Read field by field the way vLLM 0.9.2's InputBatch fills it: `logit_bias` is a list with one
+    "random" (aic_rejection_random: temperature-only rows, greedy rows mixed in), "random_topk_topp"
+    (aic_rejection_random_topk_topp: rows with top-k / top-p as well; only when `top_k_top_p`, the TOP_K_TOP_P_ENV
+    switch) or None (vLLM's sampler + RejectionSampler: min-p, penalties, logit bias, min_tokens, bad words,
+    allowed-token masks and logprobs live there, and top-k / top-p with the switch off).  Read field by field the way vLLM 0.9.2's InputBatch fills it: `logit_bias` is a list with one
     entry per request (None where unused) and is therefore never empty; `min_tokens` / `bad_words_token_ids` are dicts;
     tensors are None when no request uses them."""
     if getattr(sm, "max_num_logprobs", None) is not None or not getattr(sm, "no_penalties", True):
@@ -121,6 +130,8 @@ def hip_acceptance_kind(sm) -> Optional[str]:
         return None
     if getattr(sm, "all_greedy", False):
         return "greedy"
-    if getattr(sm, "top_k", None) is not None or getattr(sm, "top_p", None) is not None:
+    if getattr(sm, "temperature", None) is None:
         return None
-    return "random" if getattr(sm, "temperature", None) is not None else None
+    if getattr(sm, "top_k", None) is not None or getattr(sm, "top_p", None) is not None:
+        return KIND_TOP_K_TOP_P if top_k_top_p else None
+    return "random"

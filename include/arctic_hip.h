@@ -277,6 +277,30 @@ int aic_rejection_random(const void* target_logits, int logits_dtype, int64_t ro
                          const float* exp_noise, int batch, int num_draft_total, int max_spec_len,
                          int32_t* out_token_ids, int32_t* num_accepted, int32_t* last_token,
                          int32_t* hidden_index, const int64_t* target_row_index, void* workspace, void* stream);
+/* Random rows with top-k / top-p, draft_probs == None: vLLM 0.9.2's compute_probs + apply_top_k_top_p
+ * (vllm/v1/sample/rejection_sampler.py, vllm/v1/sample/ops/topk_topp_sampler.py), then the acceptance and recovery
+ * rules of aic_rejection_random over p.  top_k int32 [B] and top_p f32 [B] may each be NULL; both NULL is
+ * aic_rejection_random.  Per random row, x = logits / T in the logits dtype:
+ *   kept set   top-k (0 < k < vocab; k <= 0 or k >= vocab: none): {x >= tau_k}, tau_k the k-th largest value
+ *              counting repeats — every token tied with it stays.  top-p (p < 1; p >= 1: none): over the top-k
+ *              survivors, probabilities in f32 (exp(x - max) summed in 2^-40 fixed point: order-free), survivors
+ *              ordered ascending by (x, token index); a token is dropped iff its ascending cumulative probability
+ *              is <= 1 - p; the largest survivor (largest x, then largest index) is always kept.
+ *   ties       ties at the top-p boundary value are dropped from the lowest index upward (a stable ascending sort).
+ *   p          softmax over the kept set (f32); other tokens have p = 0 and are never recovered.
+ *   parity     vLLM rounds the cumulative sum in the logits dtype: the two can differ only where a cumulative sum
+ *              lies within that rounding of 1 - p, and where tokens' probabilities underflow to 0 (no output change).
+ * Greedy rows (T <= 0) ignore top_k / top_p (arg-max of the raw row, as aic_rejection_random); rows whose k and p
+ * disable both filters give exactly what aic_rejection_random gives.  Deterministic: no float atomics.
+ * workspace: >= aic_rejection_topk_topp_workspace_bytes(num_draft_total, vocab, logits_dtype) bytes of HBM. */
+size_t aic_rejection_topk_topp_workspace_bytes(int num_draft_total, int vocab, int logits_dtype);
+int aic_rejection_random_topk_topp(const void* target_logits, int logits_dtype, int64_t row_stride, int vocab,
+                                   const int32_t* draft_token_ids, const int32_t* cu_num_draft,
+                                   const int32_t* bonus_token_ids, const float* temperature, const double* uniform,
+                                   const float* exp_noise, const int32_t* top_k, const float* top_p, int batch,
+                                   int num_draft_total, int max_spec_len, int32_t* out_token_ids,
+                                   int32_t* num_accepted, int32_t* last_token, int32_t* hidden_index,
+                                   const int64_t* target_row_index, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A7-A11  Arctic LSTM speculator (sum_lstm) — replaces ArcticLSTMSpeculator.generate_proposals /

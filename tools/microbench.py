@@ -395,8 +395,70 @@ def rejection(B=64, k=3, V=128256):
     print(f"rejection B={B} k={k}: {us:8.1f} us  {B * k * V * 2 / 1e9 / us * 1e6 / 1e3:5.2f} TB/s")
 
 
+
+def _torch_topk_topp_accept(logits, draft, cu, bonus, temp_rows, k_rows, p_rows, u, q, req_rows, k):
+    """vLLM 0.9.2's path for the same call, restated in torch on the same GPU: x = logits / T, apply_top_k_top_p (full
+    ascending sort, softmax + cumsum in the logits dtype, scatter), softmax f32, then accept (p[draft] >= u) and
+    recovery (argmax(p / q), p[draft] := 0) with the first-rejection scan."""
+    x = (logits.float() / temp_rows.unsqueeze(1)).to(logits.dtype)
+    if k_rows is not None or p_rows is not None:
+        xs, xi = x.sort(dim=-1, descending=False)
+        if k_rows is not None:
+            xs = xs.masked_fill(xs < xs.gather(1, (xs.size(1) - k_rows).unsqueeze(1)), -float("inf"))
+        if p_rows is not None:
+            m = xs.softmax(dim=-1).cumsum(dim=-1) <= (1 - p_rows.to(x.dtype)).unsqueeze(1)
+            m[:, -1] = False
+            xs = xs.masked_fill(m, -float("inf"))
+        x = xs.scatter(-1, xi, xs)
+    p = x.softmax(dim=-1, dtype=torch.float32)
+    pd = p.gather(1, draft.long().unsqueeze(1)).squeeze(1)
+    acc = pd.double() >= u
+    p.scatter_(1, draft.long().unsqueeze(1), 0.0)
+    rec = (p / q[req_rows]).argmax(dim=-1).to(torch.int32)
+    tok = torch.where(acc, draft, rec).view(-1, k)
+    ok = acc.view(-1, k).int().cumprod(dim=1)
+    first_rej = ok.sum(dim=1)
+    out = torch.full((tok.shape[0], k + 1), -1, dtype=torch.int32, device=logits.device)
+    pos = torch.arange(k + 1, device=logits.device)
+    out[:, :k] = torch.where(pos[:k] <= first_rej.unsqueeze(1), tok, out[:, :k])
+    out[:, k] = torch.where(first_rej == k, bonus, out[:, k])
+    return out
+
+
+def rejection_topk_topp(B=64, k=3, V=128256, top_k=None, top_p=None):
+    """aic_rejection_random_topk_topp against the torch restatement of vLLM's sort-based path (same inputs)."""
+    g = torch.Generator(device=dev).manual_seed(0)
+    logits = (torch.randn(B * k, V, device=dev, generator=g) * 3).to(torch.bfloat16)
+    draft = torch.randint(0, V, (B * k,), device=dev, dtype=torch.int32, generator=g)
+    cu = (torch.arange(1, B + 1, device=dev) * k).to(torch.int32)
+    bonus = torch.zeros(B, dtype=torch.int32, device=dev)
+    temp = torch.full((B,), 0.6, device=dev)
+    u = torch.rand(B * k, dtype=torch.float64, device=dev, generator=g)
+    q = torch.empty(B, V, device=dev).exponential_(generator=g)
+    tk = None if top_k is None else torch.full((B,), top_k, dtype=torch.int32, device=dev)
+    tp = None if top_p is None else torch.full((B,), top_p, dtype=torch.float32, device=dev)
+    kw = dict(temperature=temp, uniform_probs=u, exp_noise=q, top_k=tk, top_p=tp)
+    hip = timeit(lambda: ops.rejection_sample(logits, draft, cu, bonus, k, **kw))
+    req = torch.arange(B, device=dev).repeat_interleave(k)
+    args = (logits, draft, cu, bonus, temp[req], None if tk is None else tk[req].long(), None if tp is None else tp[req],
+            u, q, req, k)
+    ref = timeit(lambda: _torch_topk_topp_accept(*args))
+    same = torch.equal(ops.rejection_sample(logits, draft, cu, bonus, k, **kw).output_token_ids,
+                       _torch_topk_topp_accept(*args))
+    passes = 1 + (2 if top_k else 0) + (1 if (top_k or top_p) else 0) + (1 if top_p else 0) + 1
+    print(f"rejtopp B={B} k={k} V={V} top_k={top_k} top_p={top_p}: hip {hip:8.1f} us ({passes} passes, "
+          f"{passes * B * k * V * 2 / 1e9 / hip * 1e6 / 1e3:5.2f} TB/s effective)   torch {ref:8.1f} us   "
+          f"x{ref / hip:5.1f}   same tokens: {same}")
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["attn", "lstm", "rej"]
+    if "rejtopp" in what:
+        for V in (128256, 201088):
+            rejection_topk_topp(V=V)                         # temperature only (aic_rejection_random)
+            rejection_topk_topp(V=V, top_p=0.9)
+            rejection_topk_topp(V=V, top_k=50)
+            rejection_topk_topp(V=V, top_k=50, top_p=0.9)
     if "attn" in what:
         attn(split=True)
         attn()
