@@ -7,7 +7,8 @@ __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.
 PARITY STATUS
   * lstm_*            : literal restatement of the reference's torch op sequence
                         (arctic_speculator.py:88-95, :648-751; fp8.py:207-223, :276-308), executed with
-                        torch CPU bf16 tensors so every op rounds where the reference's does.  The
+                        torch CPU bf16 tensors so every op rounds where the reference's does (the
+                        embedding add with its fp32 alpha and the norm's rsqrt in fp32, as on the GPU).  The
                         reference module cannot be imported (vLLM absent) and ships no fixture for it:
                         PARITY UNPINNED against the reference itself; pinned to this restatement.
   * rejection_*       : vLLM 0.9.2 RejectionSampler semantics for draft_probs=None, recalled
@@ -36,12 +37,25 @@ SQRT2 = 2 ** 0.5
 def _l2norm(x: torch.Tensor, weight=None, bias=None, eps: float = 1e-6) -> torch.Tensor:
     """MLPSpeculatorLayerNorm.forward (arctic_speculator.py:88-95), dtype-preserving like the original."""
     xf = x
-    xf = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)
+    # rsqrt in fp32, rounded once (ATen's opmath on the GPU): torch's CPU rsqrt of a small bf16 tensor can land one or two
+    # bf16 steps off the correctly rounded value, which scales the whole normalised row
+    ms = xf.pow(2).mean(-1, keepdim=True) + eps
+    xf = xf * torch.rsqrt(ms.float()).to(ms.dtype)
     x = xf.type_as(x)
     if weight is not None:
         x = weight * x
         x = x + bias
     return x
+
+
+def add_scaled(a: torch.Tensor, b: torch.Tensor, alpha: float) -> torch.Tensor:
+    """torch.add(a, b, alpha=alpha) / a.add_(b, alpha=alpha) on bf16 tensors as ATen runs it on the GPU, the reference's
+    device: fp32 opmath with alpha as an fp32 scalar, a + alpha * b contracted to one fma, rounded to bf16 once.  torch on
+    the CPU rounds alpha to bf16 first (8.15719 -> 8.1875 at n_predict = 3, Ds = 512), which is not the reference's
+    arithmetic.  In f64 the product of the fp32 alpha and a bf16 value is exact, so rounding the f64 sum to fp32 is the
+    fma's single rounding."""
+    al = float(torch.tensor(alpha, dtype=torch.float32))
+    return (a.double() + al * b.double()).float().to(a.dtype)
 
 
 def fp8_quant_per_tensor(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -56,9 +70,10 @@ def fp8_quant_per_tensor(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
 
 def lstm_generate_proposals(w: Dict[str, torch.Tensor], input_ids: torch.Tensor, hidden: torch.Tensor, k: int,
                             n_predict: int, scale_input: bool = True, fp8_head: bool = False,
-                            return_logits: bool = False, forced_tokens: torch.Tensor = None):
+                            return_logits: bool = False, forced_tokens: torch.Tensor = None, return_states: bool = False):
     """`forced_tokens` [B, k]: feed THESE tokens to the next head instead of the oracle's own arg-max (teacher forcing:
     lets a test judge every head of a row after the kernel and the oracle parted at a near-tie).
+    `return_states`: also return, per head, the bf16 state [B, Ds] the LM head reads (appended to the result tuple).
     generate_states + generate_token_ids for method == "sum_lstm", tp_size == 1
     (arctic_speculator.py:648-751), on CPU bf16.  `w` uses the module's parameter names after the
     reference loader ran: projs.{0,1}.weight = cat(forget, input, output, cell) (:886-891)."""
@@ -74,14 +89,14 @@ def lstm_generate_proposals(w: Dict[str, torch.Tensor], input_ids: torch.Tensor,
         qw, w_scale = fp8_quant_per_tensor(head_w)      # post-load hook, fp8.py:207-223
         qw_f = qw.to(torch.float32)
     gelu = torch.nn.GELU()
-    out, all_logits = [], []
+    out, all_logits, all_states = [], [], []
     for head_index in range(k):
         if head_index == 0 and scale_input:
             prev = _l2norm(prev) / SQRT2
         proj = w["projs.0.weight"] if head_index == 0 else w["projs.1.weight"]
         z = torch.nn.functional.embedding(last, w["forget_emb.0.weight"].to(dt)).repeat(1, 1, 4)
         states = torch.nn.functional.linear(prev, proj.to(dt))
-        added = torch.add(states, z, alpha=emb_weight / state_weight)
+        added = add_scaled(states, z, emb_weight / state_weight)    # torch.add(states, z, alpha=...) on the GPU
         fio, cand = added.split([Ds * 3, Ds], dim=-1)
         f, i, o = torch.sigmoid(fio).split([Ds, Ds, Ds], dim=-1)
         cand = gelu(_l2norm(cand, w["cell_ln.0.weight"].to(dt), w["cell_ln.0.bias"].to(dt)))
@@ -92,6 +107,7 @@ def lstm_generate_proposals(w: Dict[str, torch.Tensor], input_ids: torch.Tensor,
         state = st * o
         prev = state
         flat = state.flatten(0, 1)
+        all_states.append(flat)
         if fp8_head:
             qx, x_scale = fp8_quant_per_tensor(flat)    # Fp8LinearOp dynamic activation scale
             logits = ((qx.to(torch.float32) @ qw_f.t()) * (x_scale * w_scale)).to(dt)
@@ -103,20 +119,23 @@ def lstm_generate_proposals(w: Dict[str, torch.Tensor], input_ids: torch.Tensor,
         if forced_tokens is not None:
             last = forced_tokens[:, head_index].long().reshape(-1, 1)
     toks = torch.cat(out, dim=-1)
-    return (toks, all_logits) if return_logits else toks
+    res = (toks, all_logits) if return_logits else (toks,)
+    if return_states:
+        res = res + (all_states,)
+    return res if len(res) > 1 else toks
 
 
 def mlp_generate_proposals(w: Dict[str, torch.Tensor], input_ids: torch.Tensor, hidden: torch.Tensor, k: int,
                            n_predict: int, inner_dim: int, tie_weights: bool, scale_input: bool = False,
                            fp8_head: bool = False, return_logits: bool = False, forced_tokens: torch.Tensor = None,
-                           stacks: Tuple[int, int, int] = (0, 0, 0)):
+                           stacks: Tuple[int, int, int] = (0, 0, 0), return_states: bool = False):
     """ArcticMLPSpeculator.generate_states + generate_token_ids, tp_size == 1 (arctic_speculator.py:264-321), on CPU
     bf16 with the module's parameter names (emb.i / proj.i / ln.i / head.i; tied models keep stage 0, proj 0 and 1).
     `stacks` = (extra emb stages, extra proj stages, extra ln stages) of the LSTM class's "sum_rnn" form with multi-entry
     dimension lists (arctic_speculator.py:478-542): emb.i / proj.i are nn.Sequentials [base, (LayerNorm, GELU, Linear)*]
     with parameters `emb.i.{3j-2}.weight|bias`, `emb.i.{3j}.weight`; ln.i is [LayerNorm, (GELU, Linear, LayerNorm)*] with
     `ln.i.{3j-1}.weight`, `ln.i.{3j}.weight|bias`; the base modules keep the names `emb.i.weight`, `proj.i.weight`,
-    `ln.i.weight|bias` here (the loader maps `*.0.*` to them)."""
+    `ln.i.weight|bias` here (the loader maps `*.0.*` to them).  `return_states` as for lstm_generate_proposals."""
     dt = torch.bfloat16
     state_weight = 0.5 ** (0.5 / n_predict)
     emb_weight = math.sqrt((1 - state_weight ** 2) * (inner_dim / 2))
@@ -124,7 +143,7 @@ def mlp_generate_proposals(w: Dict[str, torch.Tensor], input_ids: torch.Tensor, 
     prev = hidden.to(dt).unsqueeze(1)          # b 1 d
     last = input_ids.long().unsqueeze(1)       # b 1
     gelu = torch.nn.GELU()
-    out, all_logits = [], []
+    out, all_logits, all_states = [], [], []
     for i in range(k):
         if i == 0 and scale_input:
             prev = _l2norm(prev) / SQRT2
@@ -138,7 +157,7 @@ def mlp_generate_proposals(w: Dict[str, torch.Tensor], input_ids: torch.Tensor, 
         for j in range(1, stacks[1] + 1):
             states = F.linear(gelu(_l2norm(states, w[f"proj.{sp}.{3 * j - 2}.weight"].to(dt),
                                            w[f"proj.{sp}.{3 * j - 2}.bias"].to(dt))), w[f"proj.{sp}.{3 * j}.weight"].to(dt))
-        states.add_(z, alpha=emb_weight / state_weight)
+        states = add_scaled(states, z, emb_weight / state_weight)   # states.add_(z, alpha=...) on the GPU
         y = _l2norm(states, w[f"ln.{sl}.weight"].to(dt), w[f"ln.{sl}.bias"].to(dt))
         for j in range(1, stacks[2] + 1):          # Sequential tail: GELU, Linear, LayerNorm
             y = _l2norm(F.linear(gelu(y), w[f"ln.{sl}.{3 * j - 1}.weight"].to(dt)), w[f"ln.{sl}.{3 * j}.weight"].to(dt),
@@ -146,6 +165,7 @@ def mlp_generate_proposals(w: Dict[str, torch.Tensor], input_ids: torch.Tensor, 
         states = gelu(y)
         prev = states
         flat = states.flatten(0, 1)
+        all_states.append(flat)
         head_w = w[f"head.{stage(i, 'head')}.weight"].to(dt)
         if fp8_head:
             qw, w_scale = fp8_quant_per_tensor(head_w)
@@ -159,7 +179,10 @@ def mlp_generate_proposals(w: Dict[str, torch.Tensor], input_ids: torch.Tensor, 
         if forced_tokens is not None:
             last = forced_tokens[:, i].long().reshape(-1, 1)
     toks = torch.cat(out, dim=-1)
-    return (toks, all_logits) if return_logits else toks
+    res = (toks, all_logits) if return_logits else (toks,)
+    if return_states:
+        res = res + (all_states,)
+    return res if len(res) > 1 else toks
 
 
 def merge_lstm_checkpoint(ckpt: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
