@@ -46,6 +46,14 @@ struct Elem<f16_t> {
   static __device__ __forceinline__ float round(float x) { return round_f16(x); }
 };
 
+// x = l / T (IEEE division).  The rejection sampler's compute_probs divides in place in the logits dtype, so its x is
+// rounded to that dtype; the token sampler (SAMPLER) converts to f32 first and keeps x in f32.
+template <typename T, bool SAMPLER>
+__device__ __forceinline__ float scaled_logit(float l, float temp) {
+  const float x = __fdiv_rn(l, temp);
+  return SAMPLER ? x : Elem<T>::round(x);
+}
+
 struct Best {
   float v;
   int i;
@@ -86,7 +94,8 @@ __device__ __forceinline__ int request_of_row(const int32_t* cu, int batch, int 
 // MODE 1: softmax statistics of x = round(l / T): partial (max, sum exp(x - max)).
 // MODE 2: recovered-token arg-max of p_v / q_v with p[draft] := 0, and p[draft] itself;
 //         greedy rows (T <= 0) fall back to the MODE 0 arg-max.
-template <typename T, int MODE, bool VEC_OK>
+// SAMPLER (aic_sample_topk_topp, MODE 1 only): one row per request (no cu / draft ids), x kept in f32.
+template <typename T, int MODE, bool VEC_OK, bool SAMPLER = false>
 __global__ void __launch_bounds__(256)
 logits_row_kernel(const T* __restrict__ logits, int64_t row_stride, int vocab, int seg_len, int n_splits,
                   const int32_t* __restrict__ draft_ids, const int32_t* __restrict__ cu, int batch,
@@ -113,14 +122,17 @@ logits_row_kernel(const T* __restrict__ logits, int64_t row_stride, int vocab, i
   const float* q = nullptr;
   bool greedy_row = (MODE == 0);
   if (MODE != 0) {
-    req = request_of_row(cu, batch, row);
+    req = SAMPLER ? row : request_of_row(cu, batch, row);
     temp = temperature[req];
     greedy_row = !(temp > 0.0f);
-    draft = draft_ids[row];
+    if constexpr (SAMPLER) {
+      if (!exp_noise) greedy_row = true;  // the sampler without noise: every row is greedy
+    }
+    draft = SAMPLER ? -1 : draft_ids[row];
     q = exp_noise ? exp_noise + static_cast<int64_t>(req) * vocab : nullptr;
   }
   (void)inv_t_is_greedy;
-  if (MODE == 1 && seg == 0 && threadIdx.x == 0) p_draft[row] = 0.0f;  // a draft id outside the vocab has p = 0
+  if (MODE == 1 && !SAMPLER && seg == 0 && threadIdx.x == 0) p_draft[row] = 0.0f;  // a draft id outside the vocab has p = 0
 
   float row_max = 0.0f, row_z = 1.0f;
   if (MODE == 2 && !greedy_row) {
@@ -157,7 +169,7 @@ logits_row_kernel(const T* __restrict__ logits, int64_t row_stride, int vocab, i
         best.i = idx;
       }
     } else {
-      const float x = Elem<T>::round(__fdiv_rn(l, temp));  // logits.div_(temperature) in the logits dtype
+      const float x = scaled_logit<T, SAMPLER>(l, temp);  // logits.div_(temperature) in the logits dtype (sampler: in f32)
       if (MODE == 1) {
         if (x > run_m) {
           run_z = run_z * __expf(run_m - x) + 1.0f;
@@ -422,7 +434,8 @@ static int dispatch(const void* logits, int dtype, int64_t row_stride, int vocab
 // Every launch folds the previous launch's per-segment histograms of its row in its prologue (fixed segment order) and
 // picks the next digit; per-row state and histograms are ping-ponged between launches.  Keys are 16 bits for bf16 /
 // fp16 (two digit passes) and 32 bits for f32 (four).  Rows without a filter leave the K / P launches at once and take
-// exactly the arithmetic of aic_rejection_random's mode-2 pass.
+// exactly the arithmetic of aic_rejection_random's mode-2 pass.  The token sampler at the end of this file instantiates the
+// same kernels with SAMPLER: x is not rounded, so its keys are 32 bits for every storage type.
 // ================================================================================================
 template <typename T>
 struct KeyOf;
@@ -453,6 +466,14 @@ struct KeyOf<f16_t> {
 // value-based rules: -0 and +0 are the same value
 template <typename T>
 __device__ __forceinline__ uint32_t key_of(float x) { return KeyOf<T>::key(x == 0.0f ? 0.0f : x); }
+
+// Key width and key of x: those of the storage type for the rejection sampler (x is rounded to it), 32 bits whatever
+// the storage type for the token sampler (x stays f32; rounding merges values, so 16-bit keys would keep other sets).
+template <typename T, bool SAMPLER>
+struct Arith {
+  static constexpr int kBits = SAMPLER ? 32 : KeyOf<T>::kBits;
+  static __device__ __forceinline__ uint32_t key(float x) { return SAMPLER ? key_of<float>(x) : key_of<T>(x); }
+};
 
 constexpr float kMassScale = 1099511627776.0f;  // 2^40: fixed-point unit of the mass histograms
 constexpr double kMassUnit = 1.0 / 1099511627776.0;
@@ -503,11 +524,16 @@ struct RowFilter {
   float p;
 };
 
+// SAMPLER: temperature / top_k / top_p / noise are per row (a.cu is unused)
+template <bool SAMPLER>
 __device__ __forceinline__ RowFilter row_filter(const TopkArgs& a, int row) {
   RowFilter f;
-  f.req = request_of_row(a.cu, a.batch, row);
+  f.req = SAMPLER ? row : request_of_row(a.cu, a.batch, row);
   f.temp = a.temperature[f.req];
   f.greedy = !(f.temp > 0.0f);
+  if constexpr (SAMPLER) {
+    if (!a.exp_noise) f.greedy = true;  // the sampler without noise: every row is greedy
+  }
   f.k = a.top_k ? a.top_k[f.req] : 0;
   f.p = a.top_p ? a.top_p[f.req] : 1.0f;
   f.fk = !f.greedy && f.k > 0 && f.k < a.vocab;  // k <= 0 or k >= vocab: no top-k
@@ -606,15 +632,16 @@ __device__ __forceinline__ int block_excl_scan(int c, int* s_w, int* total) {
 }
 
 
-template <typename T, int PASS, bool VEC_OK>
+template <typename T, int PASS, bool VEC_OK, bool SAMPLER = false>
 __global__ void __launch_bounds__(256) topk_row_kernel(TopkArgs a) {
-  constexpr int BITS = KeyOf<T>::kBits;
+  using A = Arith<T, SAMPLER>;
+  constexpr int BITS = A::kBits;
   const int row = blockIdx.x;
   const int seg = blockIdx.y;
   const int tid = threadIdx.x;
   const int begin = seg * a.seg_len;
   const int end = min(begin + a.seg_len, a.vocab);
-  const RowFilter f = row_filter(a, row);
+  const RowFilter f = row_filter<SAMPLER>(a, row);
   const bool filtered = f.fk || f.fp;
   if (PASS != kPassFinal && !filtered) return;  // unfiltered and greedy rows only take the final pass
   const T* base = static_cast<const T*>(a.logits) + (a.row_index ? a.row_index[row] : static_cast<int64_t>(row)) * a.row_stride;
@@ -696,7 +723,7 @@ __global__ void __launch_bounds__(256) topk_row_kernel(TopkArgs a) {
             const u64 qe = n ? s_m[s.bin] / n : 0;
             u64 d = qe ? st.prem / qe : 0;
             if (d > n) d = n;
-            if (st.pprefix == key_of<T>(row_max) && d >= n) d = n ? n - 1 : 0;
+            if (st.pprefix == A::key(row_max) && d >= n) d = n ? n - 1 : 0;
             const u64 zkept = st.zk - (st.thr - st.prem) - d * qe;
             s_zf = static_cast<float>(static_cast<double>(zkept) * kMassUnit);
             s_tau_p = st.pprefix;
@@ -742,8 +769,8 @@ __global__ void __launch_bounds__(256) topk_row_kernel(TopkArgs a) {
     };
     for_each_elem<T, VEC_OK>(base, begin, end, [&](int idx, float l) {
       (void)idx;
-      const float x = Elem<T>::round(__fdiv_rn(l, f.temp));
-      const uint32_t key = key_of<T>(x);
+      const float x = scaled_logit<T, SAMPLER>(l, f.temp);
+      const uint32_t key = A::key(x);
       if (!prefix_match(key, prefix, BITS, d)) return;
       u64 q = 0;
       if (PASS == kPassP) {
@@ -769,8 +796,8 @@ __global__ void __launch_bounds__(256) topk_row_kernel(TopkArgs a) {
     return;
   }
 
-  // ---- final pass: p over the kept set, p[draft], recovered-token partials
-  const int draft = a.draft[row];
+  // ---- final pass: p over the kept set, p[draft], recovered-token partials (SAMPLER: no draft token is removed)
+  const int draft = SAMPLER ? -1 : a.draft[row];
   const float* q = a.exp_noise + static_cast<int64_t>(f.req) * a.vocab;
   const uint32_t tau_k = s_st.kprefix, tau_p = s_tau_p;
   const float zf = s_zf;
@@ -786,16 +813,16 @@ __global__ void __launch_bounds__(256) topk_row_kernel(TopkArgs a) {
       }
       return;
     }
-    const float x = Elem<T>::round(__fdiv_rn(l, f.temp));
+    const float x = scaled_logit<T, SAMPLER>(l, f.temp);
     float p;
     if (!filtered) {
       p = __fdiv_rn(__expf(x - row_max), row_z);
     } else {
-      const uint32_t key = key_of<T>(x);
+      const uint32_t key = A::key(x);
       const bool kept = (!f.fk || key >= tau_k) && (!f.fp || key > tau_p || (key == tau_p && tie_keep));
       p = kept ? __fdiv_rn(__expf(x - row_max), zf) : 0.0f;
     }
-    if (idx == draft) {
+    if (!SAMPLER && idx == draft) {
       a.p_draft[row] = p;
       p = 0.0f;
     }
@@ -816,14 +843,14 @@ __global__ void __launch_bounds__(256) topk_row_kernel(TopkArgs a) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         lv[e] = i0 + e < end ? Elem<T>::get(base, i0 + e) : 0.0f;
-        if (i0 + e < end && key_of<T>(Elem<T>::round(__fdiv_rn(lv[e], f.temp))) == tau_p) ++c;
+        if (i0 + e < end && A::key(scaled_logit<T, SAMPLER>(lv[e], f.temp)) == tau_p) ++c;
       }
       int total;
       int rank = seen + block_excl_scan(c, s_w, &total);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         if (i0 + e >= end) continue;
-        const bool tie = key_of<T>(Elem<T>::round(__fdiv_rn(lv[e], f.temp))) == tau_p;
+        const bool tie = A::key(scaled_logit<T, SAMPLER>(lv[e], f.temp)) == tau_p;
         visit(i0 + e, lv[e], !tie || rank >= dlocal);
         rank += tie;
       }
@@ -854,6 +881,44 @@ __global__ void __launch_bounds__(256) topk_row_kernel(TopkArgs a) {
     a.part_val[row * a.n_splits + seg] = b.v;
     a.part_idx[row * a.n_splits + seg] = b.i;
   }
+}
+
+// The K / P digit passes and the final pass of one call, after its stats pass: `a` is filled but for the pass fields.
+template <typename T, bool SAMPLER>
+static int run_select_passes(TopkArgs& a, dim3 grid, bool vec_ok, hipStream_t stream) {
+  a.launch = 0;
+  a.digit = 0;
+  a.prev_pass = kPassStats;
+  a.prev_digit = 0;
+  auto go = [&](int pass, int digit) -> int {
+    a.digit = digit;
+#define AIC_TOPK_LAUNCH(P)                                                                                       \
+  if (vec_ok)                                                                                                    \
+    hipLaunchKernelGGL((topk_row_kernel<T, P, true, SAMPLER>), grid, dim3(256), 0, stream, a);                  \
+  else                                                                                                           \
+    hipLaunchKernelGGL((topk_row_kernel<T, P, false, SAMPLER>), grid, dim3(256), 0, stream, a);
+    if (pass == kPassK) {
+      AIC_TOPK_LAUNCH(kPassK)
+    } else if (pass == kPassP) {
+      AIC_TOPK_LAUNCH(kPassP)
+    } else {
+      AIC_TOPK_LAUNCH(kPassFinal)
+    }
+#undef AIC_TOPK_LAUNCH
+    a.prev_pass = pass;
+    a.prev_digit = digit;
+    ++a.launch;
+    return launch_status("topk_row_kernel");
+  };
+  constexpr int digits = Arith<T, SAMPLER>::kBits / 8;
+  int rc = AIC_OK;
+  if (a.top_k)
+    for (int d = 0; d < digits && rc == AIC_OK; ++d) rc = go(kPassK, d);
+  if (rc == AIC_OK && (a.top_k || a.top_p)) rc = go(kPassP, 0);  // Z_k (and the first top-p digit)
+  if (a.top_p)
+    for (int d = 1; d < digits && rc == AIC_OK; ++d) rc = go(kPassP, d);
+  if (rc == AIC_OK) rc = go(kPassFinal, 0);
+  return rc;
 }
 
 static void split_geometry(int rows, int vocab, int* seg_len, int* n_splits) {
@@ -921,37 +986,7 @@ static int run_rejection_topk(const void* logits, int64_t row_stride, int vocab,
     a.vocab = vocab;
     a.seg_len = seg_len;
     a.n_splits = n_splits;
-    a.launch = 0;
-    a.digit = 0;
-    a.prev_pass = kPassStats;
-    a.prev_digit = 0;
-    auto go = [&](int pass, int digit) -> int {
-      a.digit = digit;
-#define AIC_TOPK_LAUNCH(P)                                                                                       \
-  if (vec_ok)                                                                                                    \
-    hipLaunchKernelGGL((topk_row_kernel<T, P, true>), grid, dim3(256), 0, stream, a);                           \
-  else                                                                                                           \
-    hipLaunchKernelGGL((topk_row_kernel<T, P, false>), grid, dim3(256), 0, stream, a);
-      if (pass == kPassK) {
-        AIC_TOPK_LAUNCH(kPassK)
-      } else if (pass == kPassP) {
-        AIC_TOPK_LAUNCH(kPassP)
-      } else {
-        AIC_TOPK_LAUNCH(kPassFinal)
-      }
-#undef AIC_TOPK_LAUNCH
-      a.prev_pass = pass;
-      a.prev_digit = digit;
-      ++a.launch;
-      return launch_status("topk_row_kernel");
-    };
-    constexpr int digits = KeyOf<T>::kBits / 8;
-    if (top_k)
-      for (int d = 0; d < digits && rc == AIC_OK; ++d) rc = go(kPassK, d);
-    if (rc == AIC_OK) rc = go(kPassP, 0);  // Z_k (and the first top-p digit)
-    if (top_p)
-      for (int d = 1; d < digits && rc == AIC_OK; ++d) rc = go(kPassP, d);
-    if (rc == AIC_OK) rc = go(kPassFinal, 0);
+    rc = run_select_passes<T, false>(a, grid, vec_ok, stream);
     if (rc != AIC_OK) return rc;
   }
   hipLaunchKernelGGL((accept_kernel<true>), dim3(batch), dim3(64), 0, stream, part_val, part_idx, n_splits, draft, cu,
@@ -999,6 +1034,106 @@ static int dispatch_topk(const void* logits, int dtype, int64_t row_stride, int 
     case AIC_DT_F16:
       return run_rejection_topk<f16_t>(logits, row_stride, vocab, draft, cu, bonus, temperature, uniform, noise, top_k,
                                        top_p, batch, rows, max_spec_len, out, nacc, last, hidx, row_index, ws, s);
+    default:
+      set_error("unsupported logits dtype %d", dtype);
+      return AIC_ERR_UNSUPPORTED;
+  }
+}
+
+// ================================================================================================
+// Token sampler (aic_sample_topk_topp): vLLM 0.9.2's Sampler for temperature / top-k / top-p.  Sampling a token from a
+// filtered row is the recovered-token computation with no draft token removed, on x = f32(l) / T kept in f32: the
+// SAMPLER instantiations of the kernels above (32-bit keys whatever the storage type, per-row temperature and
+// filters), then one wavefront per row that reduces the per-segment partials to the token.
+// ================================================================================================
+__global__ void __launch_bounds__(64)
+sample_finish_kernel(const float* __restrict__ part_val, const int32_t* __restrict__ part_idx, int n_splits,
+                     int32_t* __restrict__ out) {
+  const int row = blockIdx.x;
+  Best b;
+  b.v = -INFINITY;
+  b.i = INT_MAX;
+  for (int s = threadIdx.x; s < n_splits; s += 64) {
+    Best o;
+    o.v = part_val[row * n_splits + s];
+    o.i = part_idx[row * n_splits + s];
+    b = better(b, o);
+  }
+  b = wave_best(b);
+  if (threadIdx.x == 0) out[row] = b.i;
+}
+
+template <typename T>
+static int run_sample(const void* logits, int64_t row_stride, int vocab, const int64_t* row_index,
+                      const float* temperature, const float* noise, const int32_t* top_k, const float* top_p, int rows,
+                      int32_t* out, void* workspace, hipStream_t stream) {
+  int seg_len, n_splits;
+  split_geometry(rows, vocab, &seg_len, &n_splits);
+  float* part_val = static_cast<float*>(workspace);  // the layout of run_rejection_topk
+  const size_t wr = static_cast<size_t>(rows);
+  int32_t* part_idx = reinterpret_cast<int32_t*>(part_val + wr * kMaxSplits);
+  float* stat_max = reinterpret_cast<float*>(part_idx + wr * kMaxSplits);
+  float* stat_sum = stat_max + wr * kMaxSplits;
+  TopState* state = reinterpret_cast<TopState*>(static_cast<char*>(workspace) + topk_region_offset(rows, vocab));
+  uint32_t* cnt = reinterpret_cast<uint32_t*>(state + 2 * wr);
+  u64* mass = reinterpret_cast<u64*>(cnt + 2 * wr * n_splits * 256);
+  const T* lg = static_cast<const T*>(logits);
+  const bool vec_ok = (reinterpret_cast<uintptr_t>(logits) % 16 == 0) && ((row_stride * sizeof(T)) % 16 == 0);
+  dim3 grid(rows, n_splits);
+  if (vec_ok)
+    hipLaunchKernelGGL((logits_row_kernel<T, 1, true, true>), grid, dim3(256), 0, stream, lg, row_stride, vocab, seg_len,
+                       n_splits, nullptr, nullptr, rows, temperature, noise, part_val, part_idx, stat_max, stat_sum,
+                       nullptr, row_index, nullptr, rows);
+  else
+    hipLaunchKernelGGL((logits_row_kernel<T, 1, false, true>), grid, dim3(256), 0, stream, lg, row_stride, vocab, seg_len,
+                       n_splits, nullptr, nullptr, rows, temperature, noise, part_val, part_idx, stat_max, stat_sum,
+                       nullptr, row_index, nullptr, rows);
+  int rc = launch_status("logits_row_kernel<stats>");
+  if (rc != AIC_OK) return rc;
+  TopkArgs a;
+  a.logits = logits;
+  a.row_stride = row_stride;
+  a.draft = nullptr;
+  a.cu = nullptr;
+  a.temperature = temperature;
+  a.exp_noise = noise;
+  a.top_k = top_k;
+  a.top_p = top_p;
+  a.row_index = row_index;
+  a.part_val = part_val;
+  a.part_idx = part_idx;
+  a.stat_max = stat_max;
+  a.stat_sum = stat_sum;
+  a.p_draft = nullptr;
+  a.state = state;
+  a.cnt = cnt;
+  a.mass = mass;
+  a.batch = rows;
+  a.rows = rows;
+  a.vocab = vocab;
+  a.seg_len = seg_len;
+  a.n_splits = n_splits;
+  rc = run_select_passes<T, true>(a, grid, vec_ok, stream);
+  if (rc != AIC_OK) return rc;
+  hipLaunchKernelGGL(sample_finish_kernel, dim3(rows), dim3(64), 0, stream, part_val, part_idx, n_splits, out);
+  return launch_status("sample_finish_kernel");
+}
+
+static int dispatch_sample(const void* logits, int dtype, int64_t row_stride, int vocab, const int64_t* row_index,
+                           const float* temperature, const float* noise, const int32_t* top_k, const float* top_p,
+                           int rows, int32_t* out, void* ws, void* stream) {
+  if (rows == 0) return AIC_OK;
+  AIC_REQUIRE(rows > 0 && vocab > 0 && row_stride >= 0, "bad arguments to the sampler");
+  AIC_REQUIRE(logits && temperature && out && ws, "null logits / temperature / output / workspace");
+  AIC_NEED_DEVICE();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (dtype) {
+    case AIC_DT_F32:
+      return run_sample<float>(logits, row_stride, vocab, row_index, temperature, noise, top_k, top_p, rows, out, ws, s);
+    case AIC_DT_BF16:
+      return run_sample<bf16_t>(logits, row_stride, vocab, row_index, temperature, noise, top_k, top_p, rows, out, ws, s);
+    case AIC_DT_F16:
+      return run_sample<f16_t>(logits, row_stride, vocab, row_index, temperature, noise, top_k, top_p, rows, out, ws, s);
     default:
       set_error("unsupported logits dtype %d", dtype);
       return AIC_ERR_UNSUPPORTED;
@@ -1054,6 +1189,18 @@ int aic_rejection_random_topk_topp(const void* target_logits, int logits_dtype, 
   return dispatch_topk(target_logits, logits_dtype, row_stride, vocab, draft_token_ids, cu_num_draft, bonus_token_ids,
                        temperature, uniform, exp_noise, top_k, top_p, batch, num_draft_total, max_spec_len,
                        out_token_ids, num_accepted, last_token, hidden_index, target_row_index, workspace, stream);
+}
+
+size_t aic_sample_workspace_bytes(int rows, int vocab, int logits_dtype) {
+  (void)logits_dtype;  // the keys are 32 bits whatever the storage type
+  return topk_workspace_bytes(rows, vocab > 0 ? vocab : 1);
+}
+
+int aic_sample_topk_topp(const void* logits, int logits_dtype, int64_t row_stride, int vocab, const int64_t* row_index,
+                         const float* temperature, const float* exp_noise, const int32_t* top_k, const float* top_p,
+                         int rows, int32_t* out_token_ids, void* workspace, void* stream) {
+  return dispatch_sample(logits, logits_dtype, row_stride, vocab, row_index, temperature, exp_noise, top_k, top_p, rows,
+                         out_token_ids, workspace, stream);
 }
 
 }  // extern "C"

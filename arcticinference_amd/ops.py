@@ -188,6 +188,43 @@ def rejection_sample(target_logits: torch.Tensor, draft_token_ids: torch.Tensor,
     return RejectionResult(out, nacc, last, hidx)
 
 
+def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, exp_noise: Optional[torch.Tensor], *,
+                  top_k: Optional[torch.Tensor] = None, top_p: Optional[torch.Tensor] = None,
+                  row_index: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int32 [rows]: one token per row as vLLM's Sampler draws it for temperature / top-k / top-p
+    (aic_sample_topk_topp): arg-max of the raw row where temperature <= 0, else argmax(p / exp_noise) with p the f32
+    softmax of f32(logits) / temperature over the kept set (k <= 0 or k >= vocab, p >= 1 disable a filter for that row).
+    `logits` [T, V] is read in place in its own dtype; `row_index` (int64 [rows]) names the rows to sample
+    (SpecDecodeMetadata.bonus_logits_indices) instead of a gathered copy, else every row is sampled.  `temperature`,
+    `top_k`, `top_p`: one value per row; `exp_noise` f32 [rows, V] (draw_sampler_noise), or None for an all-greedy
+    batch: every row is then the arg-max of its raw logits whatever its temperature."""
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("logits must be [T, V] with contiguous rows")
+    if row_index is not None and (row_index.dtype != torch.int64 or row_index.dim() != 1):
+        raise ValueError("row_index must be int64 [rows]")
+    rows = int(row_index.numel()) if row_index is not None else int(logits.size(0))
+    V = int(logits.size(1))
+    temp = temperature.reshape(-1).float()
+    tk = None if top_k is None else top_k.reshape(-1).to(torch.int32)
+    tp = None if top_p is None else top_p.reshape(-1).float()
+    if temp.numel() != rows or (tk is not None and tk.numel() != rows) or (tp is not None and tp.numel() != rows):
+        raise ValueError("temperature / top_k / top_p: one value per row")
+    if exp_noise is not None and (exp_noise.dtype != torch.float32 or tuple(exp_noise.shape) != (rows, V) or
+                                  not exp_noise.is_contiguous()):
+        raise ValueError("exp_noise must be contiguous float32 [rows, V]")
+    _need_cuda(logits, temperature, exp_noise, top_k, top_p, row_index)
+    dev = logits.device
+    out = torch.empty(rows, dtype=torch.int32, device=dev)
+    if rows == 0:
+        return out
+    dt = N.torch_dtype_code(logits.dtype)
+    ws = _workspace(N.lib().aic_sample_workspace_bytes(rows, V, dt), dev, purpose="accept")
+    N.check(N.lib().aic_sample_topk_topp(logits.data_ptr(), dt, int(logits.stride(0)), V, _ptr(row_index), temp.data_ptr(),
+                                         _ptr(exp_noise), _ptr(tk), _ptr(tp), rows, out.data_ptr(), ws.data_ptr(),
+                                         N.current_stream_ptr()))
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # A5 verify attention
 # ------------------------------------------------------------------------------------------------

@@ -32,8 +32,8 @@ import torch
 
 from . import step_context
 from .runner_logic import (INDEXING_REFERENCE, KIND_TOP_K_TOP_P, MAX_SPEC_LEN, arctic_max_spec_tokens, hip_acceptance_kind,
-                           merge_proposals, min_suffix_score, proposal_end_index, proposal_indexing, rewrite_sampled,
-                           suffix_query, top_k_top_p_switch)
+                           hip_sampler_ok, hip_sampler_switch, merge_proposals, min_suffix_score, proposal_end_index,
+                           proposal_indexing, rewrite_sampled, suffix_query, top_k_top_p_switch)
 
 logger = logging.getLogger(__name__)
 
@@ -101,6 +101,31 @@ def draw_recovery_noise(batch: int, vocab: int, num_draft_tokens, generators: di
         if num_draft_tokens[i] > 0:
             q[i].exponential_(generator=g)
     return q
+
+
+def draw_sampler_noise(rows: int, vocab: int, generators: dict, device) -> torch.Tensor:
+    """q ~ Exp(1), float32 [rows, vocab], as vLLM's random_sample draws it for the sampler (v1/sample/ops/
+    topk_topp_sampler.py, recalled): a whole-matrix draw from the default generator unless every row owns a generator,
+    then the row of every seeded request re-drawn with its generator (with or without draft tokens: the sampler serves
+    every request of the batch)."""
+    q = torch.empty((rows, vocab), dtype=torch.float32, device=device)
+    if len(generators) != rows:
+        q.exponential_()
+    for i, g in generators.items():
+        q[i].exponential_(generator=g)
+    return q
+
+
+def hip_sample(logits: torch.Tensor, sm, row_index: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """vLLM's Sampler on the HIP kernel for a SamplingMetadata that hip_sampler_ok accepts: int32 [rows] tokens of
+    `logits[row_index]` (every row when None), read in place.  All-greedy batches draw no noise."""
+    from .. import ops
+    rows = int(row_index.numel()) if row_index is not None else int(logits.shape[0])
+    if sm.all_greedy:
+        temperature = torch.zeros(rows, dtype=torch.float32, device=logits.device)
+        return ops.sample_tokens(logits, temperature, None, row_index=row_index)
+    noise = draw_sampler_noise(rows, logits.shape[-1], sm.generators, logits.device)
+    return ops.sample_tokens(logits, sm.temperature, noise, top_k=sm.top_k, top_p=sm.top_p, row_index=row_index)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -485,12 +510,20 @@ def build_model_runner_patch():
               * with ARCTIC_INFERENCE_HIP_TOP_K_TOP_P=1 (read once per step), batches whose rows also carry top-k /
                 top-p take the same route through aic_rejection_random_topk_topp (the bonus tokens stay vLLM's sampler's).
             Anything else (min-p, penalties, bias, min_tokens, masks, logprobs, and top-k / top-p with the switch off:
-            runner_logic.hip_acceptance_kind) keeps vLLM's sampler + RejectionSampler."""
+            runner_logic.hip_acceptance_kind) keeps vLLM's sampler + RejectionSampler.
+            With ARCTIC_INFERENCE_HIP_SAMPLER=1 (read once per step; runner_logic.hip_sampler_ok) vLLM's sampler itself
+            is replaced by aic_sample_topk_topp: steps without draft tokens are sampled whole, and in the random verify
+            steps above the bonus tokens are sampled from the bonus rows of `logits` in place (no gather, no f32 copy),
+            before the uniforms and the recovery noise as in vLLM, and stay on the device for the acceptance call."""
+            sm = sampling_metadata
+            hip_sampler = (hip_sampler_switch() and logits is not None and logits.is_cuda and hip_sampler_ok(sm))
             if spec_decode_metadata is None:
+                if hip_sampler:
+                    from vllm.v1.outputs import SamplerOutput
+                    return SamplerOutput(sampled_token_ids=hip_sample(logits, sm).view(-1, 1), logprobs_tensors=None)
                 return self.sampler(logits=logits, sampling_metadata=sampling_metadata)
             assert logits is not None
             md = spec_decode_metadata
-            sm = sampling_metadata
             kind = hip_acceptance_kind(sm, top_k_top_p_switch()) if logits.is_cuda else None
             if kind == "greedy":
                 from vllm.v1.outputs import SamplerOutput
@@ -501,9 +534,14 @@ def build_model_runner_patch():
                 self._arctic_rej = rej
                 self._arctic_maybe_draft_early(rej, sample_hidden_states, md.num_draft_tokens)
                 return SamplerOutput(sampled_token_ids=rej.output_token_ids, logprobs_tensors=None)
-            # indexing with a tensor copies: in-place edits of the sampler do not reach `logits`
-            bonus_logits = logits[md.bonus_logits_indices]
-            out = self.sampler(logits=bonus_logits, sampling_metadata=sampling_metadata)
+            if hip_sampler and kind in ("random", KIND_TOP_K_TOP_P):
+                from vllm.v1.outputs import SamplerOutput
+                bonus = hip_sample(logits, sm, md.bonus_logits_indices.to(torch.int64))
+                out = SamplerOutput(sampled_token_ids=bonus.view(-1, 1), logprobs_tensors=None)
+            else:
+                # indexing with a tensor copies: in-place edits of the sampler do not reach `logits`
+                bonus_logits = logits[md.bonus_logits_indices]
+                out = self.sampler(logits=bonus_logits, sampling_metadata=sampling_metadata)
             if kind in ("random", KIND_TOP_K_TOP_P):
                 filters = dict(top_k=sm.top_k, top_p=sm.top_p) if kind == KIND_TOP_K_TOP_P else {}
                 n_draft = md.num_draft_tokens

@@ -135,3 +135,26 @@ def hip_acceptance_kind(sm, top_k_top_p: bool = False) -> Optional[str]:
     if getattr(sm, "top_k", None) is not None or getattr(sm, "top_p", None) is not None:
         return KIND_TOP_K_TOP_P if top_k_top_p else None
     return "random"
+
+
+HIP_SAMPLER_ENV = "ARCTIC_INFERENCE_HIP_SAMPLER"   # 1: bonus tokens and draft-free steps sampled by aic_sample_topk_topp (default off)
+
+
+def hip_sampler_switch() -> bool:
+    return os.environ.get(HIP_SAMPLER_ENV, "0").strip().lower() in ("1", "true", "yes", "on")
+
+
+def hip_sampler_ok(sm) -> bool:
+    """Whether ops.sample_tokens (aic_sample_topk_topp: temperature, top-k, top-p; greedy rows mixed in or all-greedy)
+    can stand in for vLLM's Sampler on this SamplingMetadata.  The exclusions are those of hip_acceptance_kind: logprobs,
+    penalties, allowed-token masks, bad words, logit bias, min_tokens and min-p keep vLLM's sampler.  `top_k` / `top_p`
+    are served as tensors and as None."""
+    if getattr(sm, "max_num_logprobs", None) is not None or not getattr(sm, "no_penalties", True):
+        return False
+    if getattr(sm, "allowed_token_ids_mask", None) is not None or getattr(sm, "bad_words_token_ids", None):
+        return False
+    if any(b is not None and len(b) > 0 for b in (getattr(sm, "logit_bias", None) or ())):
+        return False
+    if getattr(sm, "min_tokens", None) or getattr(sm, "min_p", None) is not None:
+        return False
+    return bool(getattr(sm, "all_greedy", False)) or getattr(sm, "temperature", None) is not None

@@ -301,6 +301,27 @@ int aic_rejection_random_topk_topp(const void* target_logits, int logits_dtype, 
                                    int num_draft_total, int max_spec_len, int32_t* out_token_ids,
                                    int32_t* num_accepted, int32_t* last_token, int32_t* hidden_index,
                                    const int64_t* target_row_index, void* workspace, void* stream);
+/* Token sampler — vLLM 0.9.2's Sampler for temperature / top-k / top-p (vllm/v1/sample/sampler.py,
+ * vllm/v1/sample/ops/topk_topp_sampler.py: forward_native, random_sample; recalled, parity unpinned).  Serves the bonus
+ * tokens of verify steps and whole steps without draft tokens.  Row r of the call is logits[row_index ? row_index[r] : r]
+ * (row stride in elements; bf16 / fp16 / f32 rows are read in place, no f32 copy is made).  temperature f32 [rows],
+ * exp_noise f32 [rows][vocab] (q ~ Exp(1), drawn by the caller; NULL: every row is taken as greedy whatever its
+ * temperature), top_k int32 [rows] and top_p f32 [rows] may each be NULL, out_token_ids int32 [rows].  Per row:
+ *   T <= 0     arg-max of the raw row in f32, ties to the lowest index; the filters are ignored.
+ *   otherwise  x = f32(l) / T, an IEEE division KEPT IN F32.  (aic_rejection_random_topk_topp rounds x to the logits
+ *              dtype, as compute_probs does; the sampler converts to f32 first.  Rounding merges values, so the two kept
+ *              sets differ at ties of tau_k and at the top-p cut: the select here runs on 32-bit keys for every dtype.)
+ *   kept set   the contract of aic_rejection_random_topk_topp evaluated on this x: top-k {x >= tau_k} counting repeats
+ *              (ties stay); top-p over the survivors ascending by (x, index), dropped while the ascending cumulative
+ *              probability is <= 1 - p, the largest survivor always kept, boundary ties dropped from the lowest index
+ *              up; k <= 0 || k >= vocab and p >= 1 disable a filter.
+ *   token      argmax_v(p_v / q_v), p the f32 softmax over the kept set, ties to the lowest index.
+ * Deterministic (no float atomics), capturable (no host sync, no allocation); rows == 0 is a no-op.
+ * workspace: >= aic_sample_workspace_bytes(rows, vocab, logits_dtype) bytes of HBM. */
+size_t aic_sample_workspace_bytes(int rows, int vocab, int logits_dtype);
+int aic_sample_topk_topp(const void* logits, int logits_dtype, int64_t row_stride, int vocab, const int64_t* row_index,
+                         const float* temperature, const float* exp_noise, const int32_t* top_k, const float* top_p,
+                         int rows, int32_t* out_token_ids, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A7-A11  Arctic LSTM speculator (sum_lstm) — replaces ArcticLSTMSpeculator.generate_proposals /

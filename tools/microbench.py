@@ -451,8 +451,64 @@ def rejection_topk_topp(B=64, k=3, V=128256, top_k=None, top_p=None):
           f"x{ref / hip:5.1f}   same tokens: {same}")
 
 
+def _torch_sampler(logits, row_index, temp, k_rows, p_rows, q):
+    """vLLM 0.9.2's Sampler for the same call, restated in torch on the same GPU: gather the rows, f32 copy, div_ by the
+    temperature, apply_top_k_top_p in f32 (the full ascending sort when top-p is set, apply_top_k_only's topk form when
+    only top-k is), softmax f32, div_(q), arg-max."""
+    x = logits[row_index] if row_index is not None else logits
+    x = x.float().div_(temp.unsqueeze(1))
+    if p_rows is None and k_rows is not None:
+        no_k = k_rows == x.shape[1]
+        kk = k_rows.masked_fill(no_k, 1)
+        thr = x.topk(int(kk.max()), dim=1).values.gather(1, (kk - 1).unsqueeze(1))
+        thr.masked_fill_(no_k.unsqueeze(1), -float("inf"))
+        x.masked_fill_(x < thr, -float("inf"))
+    elif p_rows is not None:
+        xs, xi = x.sort(dim=-1, descending=False)
+        if k_rows is not None:
+            xs.masked_fill_(xs < xs.gather(1, (xs.size(1) - k_rows).unsqueeze(1)), -float("inf"))
+        m = xs.softmax(dim=-1).cumsum(dim=-1) <= (1 - p_rows).unsqueeze(1)
+        m[:, -1] = False
+        xs.masked_fill_(m, -float("inf"))
+        x = xs.scatter(-1, xi, xs)
+    return x.softmax(dim=-1, dtype=torch.float32).div_(q).argmax(dim=-1).to(torch.int32)
+
+
+def sample(B=64, V=128256, top_k=None, top_p=None, indexed=False, reps=3):
+    """aic_sample_topk_topp (ops.sample_tokens) against the torch restatement of vLLM's sampler: same GPU, same inputs,
+    the two timed alternately `reps` times.  `indexed`: the rows are read through row_index out of a [256, V] matrix
+    (the bonus rows of a verify step) instead of from a gathered [B, V] one."""
+    g = torch.Generator(device=dev).manual_seed(0)
+    T = 256 if indexed else B
+    logits = (torch.randn(T, V, device=dev, generator=g) * 3).to(torch.bfloat16)
+    idx = (torch.arange(B, device=dev) * (T // B) + (T // B - 1)).to(torch.int64) if indexed else None
+    temp = torch.full((B,), 0.6, device=dev)
+    q = torch.empty(B, V, device=dev).exponential_(generator=g)
+    tk = None if top_k is None else torch.full((B,), top_k, dtype=torch.int32, device=dev)
+    tp = None if top_p is None else torch.full((B,), top_p, dtype=torch.float32, device=dev)
+    hip_fn = lambda: ops.sample_tokens(logits, temp, q, top_k=tk, top_p=tp, row_index=idx)
+    ref_fn = lambda: _torch_sampler(logits, idx, temp, None if tk is None else tk.long(), tp, q)
+    hip, ref = [], []
+    for _ in range(reps):
+        hip.append(timeit(hip_fn))
+        ref.append(timeit(ref_fn))
+    same = torch.equal(hip_fn(), ref_fn())
+    passes = 1 + (4 if top_k else 0) + (1 if (top_k or top_p) else 0) + (3 if top_p else 0) + 1
+    fmt = lambda v: " / ".join(f"{x:7.1f}" for x in v)
+    print(f"sample B={B} V={V} top_k={top_k} top_p={top_p} {'row_index' if indexed else 'gathered '}: hip {fmt(hip)} us "
+          f"({passes:2d} passes, {passes * B * V * 2 / 1e9 / min(hip) * 1e6 / 1e3:5.2f} TB/s effective)   torch {fmt(ref)} us   "
+          f"x{min(ref) / max(hip):5.1f} (fastest torch / slowest hip)   same tokens: {same}", flush=True)
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["attn", "lstm", "rej"]
+    if "sample" in what:
+        for V in (128256, 201088):
+            for indexed in (False, True):
+                sample(V=V, indexed=indexed)                 # temperature only
+                sample(V=V, top_p=0.9, indexed=indexed)
+                sample(V=V, top_k=50, indexed=indexed)
+                sample(V=V, top_k=50, top_p=0.9, indexed=indexed)
     if "rejtopp" in what:
         for V in (128256, 201088):
             rejection_topk_topp(V=V)                         # temperature only (aic_rejection_random)
