@@ -55,6 +55,20 @@ inline int launch_status(const char* what) {
   return AIC_OK;
 }
 
+// Dtype rules of the attention entry points (aic_verify_attention_dt, aic_step_attention_dt), checked before any launch:
+// q and out are bf16 or f16 (one type for both), the cache has q's type or is fp8 e4m3.
+inline int attn_check_dtypes(int q_dtype, int kv_dtype) {
+  if (q_dtype != AIC_DT_BF16 && q_dtype != AIC_DT_F16) {
+    set_error("query dtype %d not supported (bf16 or fp16; out has the query's dtype)", q_dtype);
+    return AIC_ERR_UNSUPPORTED;
+  }
+  if (kv_dtype != q_dtype && kv_dtype != AIC_DT_FP8_E4M3) {
+    set_error("kv cache dtype %d not supported with query dtype %d (the query's 16-bit type, or fp8 e4m3)", kv_dtype, q_dtype);
+    return AIC_ERR_UNSUPPORTED;
+  }
+  return AIC_OK;
+}
+
 // ---- bf16 helpers (bit-level; device + host) -------------------------------------------------
 __host__ __device__ inline float bf16_to_f32(uint16_t h) {
   union { uint32_t u; float f; } v;

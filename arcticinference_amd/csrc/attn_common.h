@@ -1,6 +1,6 @@
 // Device helpers shared by the attention bodies (verify_attn.hip: decode / verify, prefill_attn.hip: chunked prefill):
-// MFMA fragment types, the 32-token KV tile image read both row-wise and transposed, the fp8 -> bf16 convert and the
-// 4-lane row reductions of the S^T layout.
+// MFMA fragment types, the 32-token KV tile image read both row-wise and transposed, the fp8 -> 16-bit converts, the
+// 16-bit element types the bodies are instantiated for (bf16 | f16) and the 4-lane row reductions of the S^T layout.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,6 +10,7 @@
 namespace aic {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 
@@ -90,6 +91,51 @@ __device__ __forceinline__ bf16x8 fp8x8_to_bf16x8(uint32_t lo, uint32_t hi) {
   return __builtin_shufflevector(__builtin_shufflevector(a, b, 0, 1, 2, 3), __builtin_shufflevector(c, d, 0, 1, 2, 3), 0, 1,
                                  2, 3, 4, 5, 6, 7);
 }
+
+// The same for an f16 body (v_cvt_scalef32_pk_f16_fp8, scale 1.0).  Exact too: e4m3 spans 2^-9 .. 448 with 4 significant
+// bits, inside f16's normal range (2^-14 .. 65504, 11 bits).
+__device__ __forceinline__ f16x8 fp8x8_to_f16x8(uint32_t lo, uint32_t hi) {
+  typedef __attribute__((ext_vector_type(2))) _Float16 f16x2_t;
+  const f16x2_t a = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(static_cast<int>(lo), 1.0f, false);
+  const f16x2_t b = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(static_cast<int>(lo), 1.0f, true);
+  const f16x2_t c = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(static_cast<int>(hi), 1.0f, false);
+  const f16x2_t d = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(static_cast<int>(hi), 1.0f, true);
+  return __builtin_shufflevector(__builtin_shufflevector(a, b, 0, 1, 2, 3), __builtin_shufflevector(c, d, 0, 1, 2, 3), 0, 1,
+                                 2, 3, 4, 5, 6, 7);
+}
+
+// The 16-bit element type of a call: q, out, a 16-bit cache and the tile images an fp8 cache is converted into all have
+// it.  Everything that moves bytes (loads, LDS-DMA, transposed LDS reads, paging, masks) is the same code for both; an
+// attention body takes one of these as its last template argument for the four places where the type matters: the MFMA,
+// the fp8 -> 16-bit tile conversion, the P operand (p = head + tail, both of the type) and the rounding of the output
+// (round-to-nearest-even, one hardware convert each).
+struct ElemBf16 {
+  typedef __bf16 elem;
+  typedef bf16x8 vec8;
+  static __device__ __forceinline__ f32x4 mfma(vec8 a, vec8 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+  }
+  static __device__ __forceinline__ vec8 from_fp8(uint32_t lo, uint32_t hi) { return fp8x8_to_bf16x8(lo, hi); }
+  static __device__ __forceinline__ elem head(float p) { return static_cast<__bf16>(p); }
+  static __device__ __forceinline__ void pin(vec8&) {}
+  static __device__ __forceinline__ elem tail(float p, elem h) { return static_cast<__bf16>(p - static_cast<float>(h)); }
+  static __device__ __forceinline__ uint16_t round(float f) { return __builtin_bit_cast(uint16_t, static_cast<__bf16>(f)); }
+};
+struct ElemF16 {
+  typedef _Float16 elem;
+  typedef f16x8 vec8;
+  static __device__ __forceinline__ f32x4 mfma(vec8 a, vec8 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+  }
+  static __device__ __forceinline__ vec8 from_fp8(uint32_t lo, uint32_t hi) { return fp8x8_to_f16x8(lo, hi); }
+  static __device__ __forceinline__ elem head(float p) { return static_cast<_Float16>(p); }
+  // long-draft body: the packed heads of a row tile are final before its tails are formed.  Left to itself the scheduler
+  // interleaves the f16 -> f32 converts of the tails with the heads' packing, and the 256-VGPR body then keeps two
+  // values in scratch across its tile loop; with this the f16 form needs 254 registers and no scratch.
+  static __device__ __forceinline__ void pin(vec8& x) { asm volatile("" : "+v"(x)); }
+  static __device__ __forceinline__ elem tail(float p, elem h) { return static_cast<_Float16>(p - static_cast<float>(h)); }
+  static __device__ __forceinline__ uint16_t round(float f) { return __builtin_bit_cast(uint16_t, static_cast<_Float16>(f)); }
+};
 
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;

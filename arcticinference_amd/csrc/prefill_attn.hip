@@ -94,9 +94,11 @@ __device__ __forceinline__ PfItem pf_item(const PrefillParams& P, int wgi) {
 // D = head size: 128 (bf16 or fp8 cache) or 64 (bf16 cache; the verify bodies' rule).  WIN: the layer has a sliding
 // window (P.window > 0).  Without one the window terms fold away and the tile loop is the plain causal one: they cost
 // the D = 128 body ~2.5 % when kept as runtime tests (measured on the Llama-8B 2048-token chunk at ctx 4096).
-template <int D, bool KV8, bool WIN>
+// E = the call's 16-bit element type (attn_common.h: ElemBf16 | ElemF16): q, out, a 16-bit cache and the tile images.
+template <int D, bool KV8, bool WIN, typename E = ElemBf16>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) prefill_attn_kernel(PrefillParams P) {
-  static_assert(D == 128 || (D == 64 && !KV8), "head size 128, or 64 with a bf16 cache");
+  static_assert(D == 128 || (D == 64 && !KV8), "head size 128, or 64 with a 16-bit cache");
+  using V8 = typename E::vec8;
   constexpr int DT = D / 16;   // 16-wide output tiles
   constexpr int NS = D / 32;   // k-steps of mfma_f32_16x16x32_bf16 per S tile
   constexpr int ES = KV8 ? 1 : 2;
@@ -217,10 +219,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
     }
     if (KV8) {
       const int ti = tid >> 3, ch = 2 * (tid & 7);
-      *reinterpret_cast<bf16x8*>(kt + v_tile_off(ti, ch)) = fp8x8_to_bf16x8(kr0.x, kr0.y);
-      *reinterpret_cast<bf16x8*>(kt + v_tile_off(ti, ch + 1)) = fp8x8_to_bf16x8(kr0.z, kr0.w);
-      *reinterpret_cast<bf16x8*>(vt + v_tile_off(ti, ch)) = fp8x8_to_bf16x8(vr0.x, vr0.y);
-      *reinterpret_cast<bf16x8*>(vt + v_tile_off(ti, ch + 1)) = fp8x8_to_bf16x8(vr0.z, vr0.w);
+      *reinterpret_cast<V8*>(kt + v_tile_off(ti, ch)) = E::from_fp8(kr0.x, kr0.y);
+      *reinterpret_cast<V8*>(kt + v_tile_off(ti, ch + 1)) = E::from_fp8(kr0.z, kr0.w);
+      *reinterpret_cast<V8*>(vt + v_tile_off(ti, ch)) = E::from_fp8(vr0.x, vr0.y);
+      *reinterpret_cast<V8*>(vt + v_tile_off(ti, ch + 1)) = E::from_fp8(vr0.z, vr0.w);
     } else if (D == 64) {
       const int ti = tid >> 3, ch = tid & 7;
       *reinterpret_cast<uint4*>(kt + tile_off<64>(ti, ch)) = kr0;
@@ -238,21 +240,21 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
   auto compute_tile = [&](int buf, int tt) {
     const char* kt = reinterpret_cast<const char*>(lds[buf][0]);
     const char* vt = reinterpret_cast<const char*>(lds[buf][1]);
-    bf16x8 kf[2][NS];  // A operand: key 16 th + c16, d = 32 s + 8 g + j
+    V8 kf[2][NS];  // A operand: key 16 th + c16, d = 32 s + 8 g + j
 #pragma unroll
     for (int th = 0; th < 2; ++th)
 #pragma unroll
-      for (int s = 0; s < NS; ++s) kf[th][s] = *reinterpret_cast<const bf16x8*>(kt + tile_off<D>(16 * th + c16, 4 * s + g));
+      for (int s = 0; s < NS; ++s) kf[th][s] = *reinterpret_cast<const V8*>(kt + tile_off<D>(16 * th + c16, 4 * s + g));
     // the tile crosses the causal edge of a row of the wave, or (window) holds a key at or below a row's lim - window
     const bool need_mask = tt + kTile - 1 > w_lim_lo || (WIN && tt <= w_lim_hi - wnd);
-    bf16x8 pf[kPfMT], pl[kPfMT];  // P = head + tail (bf16 each): one bf16 P would put 2^-9 on every weight
+    V8 pf[kPfMT], pl[kPfMT];  // P = head + tail (E each): one bf16 P would put 2^-9 on every weight
 #pragma unroll
     for (int mt = 0; mt < kPfMT; ++mt) {
       f32x4 a0 = f32x4{0.f, 0.f, 0.f, 0.f}, a1 = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
-        a0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[0][s], __builtin_bit_cast(bf16x8, qf[mt][s]), a0, 0, 0, 0);
-        a1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[1][s], __builtin_bit_cast(bf16x8, qf[mt][s]), a1, 0, 0, 0);
+        a0 = E::mfma(kf[0][s], __builtin_bit_cast(V8, qf[mt][s]), a0);
+        a1 = E::mfma(kf[1][s], __builtin_bit_cast(V8, qf[mt][s]), a1);
       }
       // lane (c16, g) holds row c16's scores of keys tt + 4 g + e (a0) and tt + 16 + 4 g + e (a1)
       float sc[8];
@@ -287,8 +289,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[e], scale_log2, -m_use));
-        pf[mt][e] = static_cast<__bf16>(p);
-        pl[mt][e] = static_cast<__bf16>(p - static_cast<float>(pf[mt][e]));
+        pf[mt][e] = E::head(p);
+        pl[mt][e] = E::tail(p, pf[mt][e]);
         ls += p;
       }
       l_run[mt] += ls;
@@ -302,12 +304,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
       const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(const_cast<char*>(a_lo)));
       const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(const_cast<char*>(a_hi)));
       typedef __attribute__((ext_vector_type(8))) short s16x8;
-      const bf16x8 vfrag = __builtin_bit_cast(bf16x8, static_cast<s16x8>(__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7)));
+      const V8 vfrag = __builtin_bit_cast(V8, static_cast<s16x8>(__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7)));
 #pragma unroll
       for (int mt = 0; mt < kPfMT; ++mt)
       {
-        o_acc[mt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfrag, pf[mt], o_acc[mt][dt], 0, 0, 0);
-        o_acc[mt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfrag, pl[mt], o_acc[mt][dt], 0, 0, 0);
+        o_acc[mt][dt] = E::mfma(vfrag, pf[mt], o_acc[mt][dt]);
+        o_acc[mt][dt] = E::mfma(vfrag, pl[mt], o_acc[mt][dt]);
       }
     }
   };
@@ -340,10 +342,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
       uint16_t* op = P.out + static_cast<int64_t>(q0 + pos) * P.out_stride + static_cast<int64_t>(h * G + gq) * D + 4 * g;
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
-        const uint32_t lo = static_cast<uint32_t>(f32_to_bf16(o_acc[mt][dt][0] * inv)) |
-                            (static_cast<uint32_t>(f32_to_bf16(o_acc[mt][dt][1] * inv)) << 16);
-        const uint32_t hi = static_cast<uint32_t>(f32_to_bf16(o_acc[mt][dt][2] * inv)) |
-                            (static_cast<uint32_t>(f32_to_bf16(o_acc[mt][dt][3] * inv)) << 16);
+        const uint32_t lo = static_cast<uint32_t>(E::round(o_acc[mt][dt][0] * inv)) |
+                            (static_cast<uint32_t>(E::round(o_acc[mt][dt][1] * inv)) << 16);
+        const uint32_t hi = static_cast<uint32_t>(E::round(o_acc[mt][dt][2] * inv)) |
+                            (static_cast<uint32_t>(E::round(o_acc[mt][dt][3] * inv)) << 16);
         *reinterpret_cast<uint2*>(op + dt * 16) = make_uint2(lo, hi);
       }
     } else {
@@ -360,7 +362,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
 
 // Merge of the split partials: one wave per row of the prefill grid (lane = two elements of the head dimension; D = 64
 // leaves the upper half of the wave idle).
-template <int D>
+template <int D, typename E = ElemBf16>
 __global__ void __launch_bounds__(256) prefill_combine_kernel(PrefillParams P) {
   const int lane = threadIdx.x & 63;
   if (2 * lane >= D) return;
@@ -391,7 +393,7 @@ __global__ void __launch_bounds__(256) prefill_combine_kernel(PrefillParams P) {
   const float inv = L > 0.0f ? 1.0f / L : 0.0f;
   uint16_t* op = P.out + static_cast<int64_t>(q0 + pos) * P.out_stride + static_cast<int64_t>(it.h * G + gq) * D + 2 * lane;
   *reinterpret_cast<uint32_t*>(op) =
-      static_cast<uint32_t>(f32_to_bf16(acc0 * inv)) | (static_cast<uint32_t>(f32_to_bf16(acc1 * inv)) << 16);
+      static_cast<uint32_t>(E::round(acc0 * inv)) | (static_cast<uint32_t>(E::round(acc1 * inv)) << 16);
 }
 
 // Rows of the decode part of a mixed step: gather (dst[i] = src[index[i]]) or scatter (dst[index[i]] = src[i]) of
@@ -440,21 +442,26 @@ size_t pf_workspace_bytes(int n_prefill, int max_prefill_q_len, int num_q_heads,
   return pf_partial_bytes(pf_grid(n_prefill, max_prefill_q_len, num_q_heads, num_kv_heads, 0), head_size) + 256;
 }
 
-template <int D, bool WIN>
-int launch_prefill(const PrefillParams& P, bool kv8, dim3 grid, hipStream_t s) {
+template <int D, bool WIN, typename E>
+int launch_prefill_e(const PrefillParams& P, bool kv8, dim3 grid, hipStream_t s) {
   if constexpr (D == 128) {
     if (kv8)
-      hipLaunchKernelGGL((prefill_attn_kernel<128, true, WIN>), grid, dim3(256), 0, s, P);
+      hipLaunchKernelGGL((prefill_attn_kernel<128, true, WIN, E>), grid, dim3(256), 0, s, P);
     else
-      hipLaunchKernelGGL((prefill_attn_kernel<128, false, WIN>), grid, dim3(256), 0, s, P);
+      hipLaunchKernelGGL((prefill_attn_kernel<128, false, WIN, E>), grid, dim3(256), 0, s, P);
   } else {
-    hipLaunchKernelGGL((prefill_attn_kernel<D, false, WIN>), grid, dim3(256), 0, s, P);
+    hipLaunchKernelGGL((prefill_attn_kernel<D, false, WIN, E>), grid, dim3(256), 0, s, P);
   }
   int rc = launch_status("prefill_attn_kernel");
   if (rc != AIC_OK || P.n_splits == 1) return rc;
   const int64_t rows = static_cast<int64_t>(P.n_wg) * kPfRows;
-  hipLaunchKernelGGL(prefill_combine_kernel<D>, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), 0, s, P);
+  hipLaunchKernelGGL((prefill_combine_kernel<D, E>), dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), 0, s, P);
   return launch_status("prefill_combine_kernel");
+}
+
+template <int D, bool WIN>
+int launch_prefill(const PrefillParams& P, bool kv8, bool f16, dim3 grid, hipStream_t s) {
+  return f16 ? launch_prefill_e<D, WIN, ElemF16>(P, kv8, grid, s) : launch_prefill_e<D, WIN, ElemBf16>(P, kv8, grid, s);
 }
 
 }  // namespace
@@ -499,6 +506,25 @@ int aic_step_attention_win(const void* q, int64_t q_stride, const void* k_cache,
                            const int32_t* decode_query_start_loc, const int32_t* decode_token_index,
                            int num_decode_tokens, int max_decode_q_len, int max_prefill_q_len, int sliding_window,
                            const float* sinks, void* stream) {
+  return aic_step_attention_dt(q, q_stride, k_cache, v_cache, block_stride, kv_dtype, k_scale, v_scale, block_table,
+                               max_blocks_per_seq, seq_lens, query_start_loc, batch, num_tokens, num_q_heads, num_kv_heads,
+                               head_size, block_size, sm_scale, out, out_stride, workspace, workspace_bytes, max_seq_len,
+                               req_lists, n_short, n_prefill, n_long, decode_query_start_loc, decode_token_index,
+                               num_decode_tokens, max_decode_q_len, max_prefill_q_len, sliding_window, sinks, AIC_DT_BF16,
+                               stream);
+}
+
+// The whole-step call for a model of either 16-bit type: one attention call per step whatever the dtype, as the
+// reference has it (arctic_inference/vllm/ulysses.py:510).  q_dtype is the type of q AND of out.
+int aic_step_attention_dt(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache, int64_t block_stride,
+                          int kv_dtype, const float* k_scale, const float* v_scale, const int32_t* block_table,
+                          int max_blocks_per_seq, const int32_t* seq_lens, const int32_t* query_start_loc, int batch,
+                          int num_tokens, int num_q_heads, int num_kv_heads, int head_size, int block_size,
+                          float sm_scale, void* out, int64_t out_stride, void* workspace, size_t workspace_bytes,
+                          int max_seq_len, const int32_t* req_lists, int n_short, int n_prefill, int n_long,
+                          const int32_t* decode_query_start_loc, const int32_t* decode_token_index,
+                          int num_decode_tokens, int max_decode_q_len, int max_prefill_q_len, int sliding_window,
+                          const float* sinks, int q_dtype, void* stream) {
   if (batch == 0 || num_tokens == 0) return AIC_OK;
   AIC_REQUIRE(sliding_window >= 0, "sliding_window must be >= 0 (0 = none)");
   AIC_REQUIRE(req_lists && n_short >= 0 && n_prefill >= 0 && n_long >= 0 && n_short + n_prefill + n_long == batch,
@@ -506,12 +532,12 @@ int aic_step_attention_win(const void* q, int64_t q_stride, const void* k_cache,
   const int32_t* short_reqs = req_lists;
   const int32_t* prefill_reqs = req_lists + n_short;
   const int32_t* long_reqs = req_lists + n_short + n_prefill;
-  if (n_prefill == 0)  // a decode step: exactly aic_verify_attention_win
-    return aic_verify_attention_win(q, q_stride, k_cache, v_cache, block_stride, kv_dtype, k_scale, v_scale, block_table,
-                                    max_blocks_per_seq, seq_lens, query_start_loc, batch, num_tokens, max_decode_q_len,
-                                    num_q_heads, num_kv_heads, head_size, block_size, sm_scale, out, out_stride, workspace,
-                                    workspace_bytes, max_seq_len, short_reqs, n_short, long_reqs, n_long, sliding_window,
-                                    sinks, stream);
+  if (n_prefill == 0)  // a decode step: exactly aic_verify_attention_dt
+    return aic_verify_attention_dt(q, q_stride, k_cache, v_cache, block_stride, kv_dtype, k_scale, v_scale, block_table,
+                                   max_blocks_per_seq, seq_lens, query_start_loc, batch, num_tokens, max_decode_q_len,
+                                   num_q_heads, num_kv_heads, head_size, block_size, sm_scale, out, out_stride, workspace,
+                                   workspace_bytes, max_seq_len, short_reqs, n_short, long_reqs, n_long, sliding_window,
+                                   sinks, q_dtype, stream);
 
   AIC_REQUIRE(q && k_cache && v_cache && block_table && seq_lens && query_start_loc && out && workspace,
               "null pointer argument to aic_step_attention");
@@ -519,14 +545,11 @@ int aic_step_attention_win(const void* q, int64_t q_stride, const void* k_cache,
               "num_q_heads must be a positive multiple of num_kv_heads");
   AIC_REQUIRE(num_q_heads / num_kv_heads <= 8, "prefill body: at most 8 query heads per kv head");
   AIC_REQUIRE(max_prefill_q_len > 0 && max_seq_len > 0 && max_blocks_per_seq > 0, "non-positive size argument");
-  if (kv_dtype != AIC_DT_BF16 && kv_dtype != AIC_DT_FP8_E4M3) {
-    set_error("kv cache dtype %d not supported (bf16 or fp8 e4m3)", kv_dtype);
-    return AIC_ERR_UNSUPPORTED;
-  }
-  const bool kv8 = kv_dtype == AIC_DT_FP8_E4M3;
+  if (const int drc = attn_check_dtypes(q_dtype, kv_dtype); drc != AIC_OK) return drc;
+  const bool kv8 = kv_dtype == AIC_DT_FP8_E4M3, f16 = q_dtype == AIC_DT_F16;
   if (head_size != 128 && !(head_size == 64 && !kv8)) {
-    set_error("prefill body: head_size %d with a%s cache not supported (128, or 64 with a bf16 cache)", head_size,
-              kv8 ? "n fp8" : " bf16");
+    set_error("prefill body: head_size %d with a%s cache not supported (128, or 64 with a 16-bit cache)", head_size,
+              kv8 ? "n fp8" : " 16-bit");
     return AIC_ERR_UNSUPPORTED;
   }
   AIC_REQUIRE(!kv8 || (k_scale && v_scale), "an fp8 kv cache needs k_scale and v_scale (device scalars)");
@@ -560,12 +583,12 @@ int aic_step_attention_win(const void* q, int64_t q_stride, const void* k_cache,
                        q_stride * 2, q_dec, static_cast<int64_t>(row_bytes), decode_token_index, static_cast<int>(row_bytes), 0);
     int rc = launch_status("step_rows_kernel");
     if (rc != AIC_OK) return rc;
-    rc = aic_verify_attention_win(q_dec, num_q_heads * head_size, k_cache, v_cache, block_stride, kv_dtype, k_scale,
-                                  v_scale, block_table, max_blocks_per_seq, seq_lens, decode_query_start_loc, batch,
-                                  num_decode_tokens, max_decode_q_len, num_q_heads, num_kv_heads, head_size, block_size,
-                                  sm_scale, o_dec, num_q_heads * head_size, dec + 2 * stage,
-                                  workspace_bytes - pf_bytes - 2 * stage, max_seq_len, short_reqs, n_short + n_prefill,
-                                  long_reqs, n_long, sliding_window, sinks, stream);
+    rc = aic_verify_attention_dt(q_dec, num_q_heads * head_size, k_cache, v_cache, block_stride, kv_dtype, k_scale,
+                                 v_scale, block_table, max_blocks_per_seq, seq_lens, decode_query_start_loc, batch,
+                                 num_decode_tokens, max_decode_q_len, num_q_heads, num_kv_heads, head_size, block_size,
+                                 sm_scale, o_dec, num_q_heads * head_size, dec + 2 * stage,
+                                 workspace_bytes - pf_bytes - 2 * stage, max_seq_len, short_reqs, n_short + n_prefill,
+                                 long_reqs, n_long, sliding_window, sinks, q_dtype, stream);
     if (rc != AIC_OK) return rc;
     hipLaunchKernelGGL(step_rows_kernel, dim3(num_decode_tokens), dim3(256), 0, s, static_cast<const char*>(o_dec),
                        static_cast<int64_t>(row_bytes), static_cast<char*>(out), out_stride * 2, decode_token_index,
@@ -605,8 +628,8 @@ int aic_step_attention_win(const void* q, int64_t q_stride, const void* k_cache,
   P.sinks = sinks;
   const dim3 grid(static_cast<unsigned>(gr.n_wg) * gr.n_splits);
   if (head_size == 128)
-    return sliding_window > 0 ? launch_prefill<128, true>(P, kv8, grid, s) : launch_prefill<128, false>(P, kv8, grid, s);
-  return sliding_window > 0 ? launch_prefill<64, true>(P, kv8, grid, s) : launch_prefill<64, false>(P, kv8, grid, s);
+    return sliding_window > 0 ? launch_prefill<128, true>(P, kv8, f16, grid, s) : launch_prefill<128, false>(P, kv8, f16, grid, s);
+  return sliding_window > 0 ? launch_prefill<64, true>(P, kv8, f16, grid, s) : launch_prefill<64, false>(P, kv8, f16, grid, s);
 }
 
 }  // extern "C"

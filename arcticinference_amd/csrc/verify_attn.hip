@@ -130,16 +130,17 @@ constexpr float kLazySlack = 6.0f;   // long-draft body: a row's adopted maximum
 
 // Online-softmax update of one 16-row query tile against one 32-token KV tile, in the S^T layout: the lane owns
 // query row c16 and the 8 tokens tt + 16 th + 4 g + e.  Scores stay raw; the scale (folded with log2 e, v_exp_f32 is base 2)
-// enters the exponent's fma.  Produces P as bf16 head + tail fragments (B operand of O^T = V^T P^T).
+// enters the exponent's fma.  Produces P as head + tail fragments of the call's 16-bit type E (B operand of O^T = V^T P^T).
 // r04: the row maximum is LAZY, as in the long-draft body — a row keeps the maximum it last adopted (m_run, scaled; -inf =
 // nothing visible yet) while no score of the tile exceeds it by more than kLazySlack: the common tile has no cross-lane
 // exchange, no alpha and no rescale; l_part is this LANE's share of the row's sum (rowgroup_sum once, after the loop).
 // Masking is a real branch (the uniform need_mask test used to be if-converted: 16 selects, 22 compares and 24 scalar
 // ands on EVERY tile — ~60 of the fp8 body's ~380 instructions per tile, a loop SQ counters show issue-bound).
-template <int DT>
+template <int DT, typename E>
 __device__ __forceinline__ void softmax_tile(const f32x4& s0, const f32x4& s1, bool need_mask, bool row_ok, int tt,
                                              int g, int t_end, int limit, int wnd, float scale_log2, float inv_scale,
-                                             float& m_run, float& l_part, f32x4 (&o)[DT], bf16x8& pf, bf16x8& pl) {
+                                             float& m_run, float& l_part, f32x4 (&o)[DT], typename E::vec8& pf,
+                                             typename E::vec8& pl) {
   float sc[8];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
@@ -180,8 +181,8 @@ __device__ __forceinline__ void softmax_tile(const f32x4& s0, const f32x4& s1, b
   l_part += p0 + p1;
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
-    pf[e] = static_cast<__bf16>(pv[e]);
-    pl[e] = static_cast<__bf16>(pv[e] - static_cast<float>(pf[e]));
+    pf[e] = E::head(pv[e]);
+    pl[e] = E::tail(pv[e], pf[e]);
   }
 }
 
@@ -219,9 +220,11 @@ struct ShortLds {
 // HD = head size: 128, or 64 with a bf16 cache (gpt-oss).  A 64-wide bf16 head is a 128-byte token row like a 128-wide fp8
 // one: K and V are fetched with the fp8 form's lane mapping (two 16-byte K loads per token group, four V loads per tile),
 // used as they are (no conversion), with two k-steps per score MFMA chain and four 16-wide output tiles.
-template <int MTQ, int HPW, bool KV8, int NW, int HD = kD>
+// E = the call's 16-bit element type (attn_common.h: ElemBf16 | ElemF16): what "bf16" stands for above in an f16 call.
+template <int MTQ, int HPW, bool KV8, int NW, int HD = kD, typename E = ElemBf16>
 __device__ __forceinline__ void verify_attn_body(const AttnParams& P, uint4* v_lds_raw, const int bx, const int by) {
-  static_assert(HD == 128 || (HD == 64 && !KV8), "head size 128, or 64 with a bf16 cache");
+  static_assert(HD == 128 || (HD == 64 && !KV8), "head size 128, or 64 with a 16-bit cache");
+  using V8 = typename E::vec8;
   constexpr bool ROW128 = KV8 || HD == 64;   // bytes of a token row of one head: 128 (else 256)
   constexpr int DT = HD / 16;                // 16-wide tiles of the output's head dimension
   constexpr bool WH = HPW == NW;
@@ -426,8 +429,8 @@ __device__ __forceinline__ void verify_attn_body(const AttnParams& P, uint4* v_l
   if (KV8) {                                                                                                   \
     if ((iv_) < 4) {                                                                                           \
       const int tok_ = 8 * (iv_) + (lane >> 3), ch_ = 2 * (lane & 7);                                          \
-      *reinterpret_cast<bf16x8*>(vt + v_tile_off(tok_, ch_)) = fp8x8_to_bf16x8(reg_.x, reg_.y);                \
-      *reinterpret_cast<bf16x8*>(vt + v_tile_off(tok_, ch_ + 1)) = fp8x8_to_bf16x8(reg_.z, reg_.w);            \
+      *reinterpret_cast<V8*>(vt + v_tile_off(tok_, ch_)) = E::from_fp8(reg_.x, reg_.y);                        \
+      *reinterpret_cast<V8*>(vt + v_tile_off(tok_, ch_ + 1)) = E::from_fp8(reg_.z, reg_.w);                    \
     }                                                                                                          \
   } else if (HD == 64) {                                                                                       \
     if ((iv_) < 4) *reinterpret_cast<uint4*>(vt + tile_off<64>(8 * (iv_) + (lane >> 3), lane & 7)) = reg_;     \
@@ -462,14 +465,13 @@ __device__ __forceinline__ void verify_attn_body(const AttnParams& P, uint4* v_l
 #pragma unroll
       for (int mt = 0; mt < MTQ; ++mt) {
         f32x4 a0 = f32x4{0.f, 0.f, 0.f, 0.f}, a1 = f32x4{0.f, 0.f, 0.f, 0.f};
-#define AIC_QK(acc_, kfrag_, s_) \
-  acc_ = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfrag_, __builtin_bit_cast(bf16x8, qf[mt][s_]), acc_, 0, 0, 0);
-#define AIC_B16(r_) __builtin_bit_cast(bf16x8, r_)
+#define AIC_QK(acc_, kfrag_, s_) acc_ = E::mfma(kfrag_, __builtin_bit_cast(V8, qf[mt][s_]), acc_);
+#define AIC_B16(r_) __builtin_bit_cast(V8, r_)
         if (KV8) {
-          AIC_QK(a0, fp8x8_to_bf16x8(k00.x, k00.y), 0) AIC_QK(a0, fp8x8_to_bf16x8(k00.z, k00.w), 1)
-          AIC_QK(a0, fp8x8_to_bf16x8(k01.x, k01.y), 2) AIC_QK(a0, fp8x8_to_bf16x8(k01.z, k01.w), 3)
-          AIC_QK(a1, fp8x8_to_bf16x8(k10.x, k10.y), 0) AIC_QK(a1, fp8x8_to_bf16x8(k10.z, k10.w), 1)
-          AIC_QK(a1, fp8x8_to_bf16x8(k11.x, k11.y), 2) AIC_QK(a1, fp8x8_to_bf16x8(k11.z, k11.w), 3)
+          AIC_QK(a0, E::from_fp8(k00.x, k00.y), 0) AIC_QK(a0, E::from_fp8(k00.z, k00.w), 1)
+          AIC_QK(a0, E::from_fp8(k01.x, k01.y), 2) AIC_QK(a0, E::from_fp8(k01.z, k01.w), 3)
+          AIC_QK(a1, E::from_fp8(k10.x, k10.y), 0) AIC_QK(a1, E::from_fp8(k10.z, k10.w), 1)
+          AIC_QK(a1, E::from_fp8(k11.x, k11.y), 2) AIC_QK(a1, E::from_fp8(k11.z, k11.w), 3)
         } else if (HD == 64) {      // two k-steps: d = 8 g + j and 32 + 8 g + j
           AIC_QK(a0, AIC_B16(k00), 0) AIC_QK(a0, AIC_B16(k01), 1)
           AIC_QK(a1, AIC_B16(k10), 0) AIC_QK(a1, AIC_B16(k11), 1)
@@ -486,12 +488,12 @@ __device__ __forceinline__ void verify_attn_body(const AttnParams& P, uint4* v_l
       AIC_LOAD_K(tn, pages_next)
       pages_next = tile_pages(tn + kTile);
 
-      bf16x8 pfrag[MTQ], pfrag_lo[MTQ];
+      V8 pfrag[MTQ], pfrag_lo[MTQ];
       // the tile reaches the causal edge / range end, or (window) lies below the last row's lower bound ctx - window
       const bool need_mask = tn > t_end || tn > ctx - q_len + 1 || tt < ctx - wnd;
 #pragma unroll
       for (int mt = 0; mt < MTQ; ++mt) {
-        softmax_tile<DT>(st[mt][0], st[mt][1], need_mask, row_ok[mt], tt, g, t_end, ctx - q_len + row_pos[mt], wnd, scale_log2,
+        softmax_tile<DT, E>(st[mt][0], st[mt][1], need_mask, row_ok[mt], tt, g, t_end, ctx - q_len + row_pos[mt], wnd, scale_log2,
                          inv_scale, m_run[mt], l_run[mt], o_acc[mt], pfrag[mt], pfrag_lo[mt]);
       }
 
@@ -509,11 +511,11 @@ __device__ __forceinline__ void verify_attn_body(const AttnParams& P, uint4* v_l
               (s16x4 __attribute__((address_space(3)))*)(const_cast<char*>(a_hi)));
           typedef __attribute__((ext_vector_type(8))) short s16x8;
           const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-          const bf16x8 vfrag = __builtin_bit_cast(bf16x8, both);
+          const V8 vfrag = __builtin_bit_cast(V8, both);
 #pragma unroll
           for (int mt = 0; mt < MTQ; ++mt) {
-            o_acc[mt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfrag, pfrag[mt], o_acc[mt][dt], 0, 0, 0);
-            o_acc[mt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfrag, pfrag_lo[mt], o_acc[mt][dt], 0, 0, 0);
+            o_acc[mt][dt] = E::mfma(vfrag, pfrag[mt], o_acc[mt][dt]);
+            o_acc[mt][dt] = E::mfma(vfrag, pfrag_lo[mt], o_acc[mt][dt]);
           }
         }
       }
@@ -529,13 +531,13 @@ __device__ __forceinline__ void verify_attn_body(const AttnParams& P, uint4* v_l
 #undef AIC_V_ADDR
 #undef AIC_STORE_V
 
-  // finished rows (direct mode): normalise, round to bf16, 8 bytes per lane and 16-wide d tile
+  // finished rows (direct mode): normalise, round to E, 8 bytes per lane and 16-wide d tile
   auto store_final = [&](int mt, const f32x4 (&o)[DT], float inv_l, int64_t tok, int hq) {
     uint16_t* op = P.out + tok * P.out_stride + static_cast<int64_t>(hq) * HD + 4 * g;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) {
-      const uint32_t lo = static_cast<uint32_t>(f32_to_bf16(o[dt][0] * inv_l)) | (static_cast<uint32_t>(f32_to_bf16(o[dt][1] * inv_l)) << 16);
-      const uint32_t hi = static_cast<uint32_t>(f32_to_bf16(o[dt][2] * inv_l)) | (static_cast<uint32_t>(f32_to_bf16(o[dt][3] * inv_l)) << 16);
+      const uint32_t lo = static_cast<uint32_t>(E::round(o[dt][0] * inv_l)) | (static_cast<uint32_t>(E::round(o[dt][1] * inv_l)) << 16);
+      const uint32_t hi = static_cast<uint32_t>(E::round(o[dt][2] * inv_l)) | (static_cast<uint32_t>(E::round(o[dt][3] * inv_l)) << 16);
       *reinterpret_cast<uint2*>(op + dt * 16) = make_uint2(lo, hi);
     }
   };
@@ -664,26 +666,26 @@ __device__ __forceinline__ void verify_attn_body(const AttnParams& P, uint4* v_l
 // or a k = 3 draft (<= 16 rows with Hq/Hkv <= 4); suffix drafts of 4-7 tokens (17-32 rows; 46 % of all suffix drafts in
 // the r02 bench, `bench.py --qlen-hist`) used to go through the shared-tile long-draft body, where a request costs ~6 us
 // per layer whatever its length, against ~2.7 us for a workgroup of this streaming body.
-template <int HPW, bool KV8, int NW, int HD = kD>
+template <int HPW, bool KV8, int NW, int HD = kD, typename E = ElemBf16>
 __device__ __forceinline__ void verify_attn_body_dual(const AttnParams& P, uint4* v_lds_raw, const int bx, const int by) {
   if (bx >= P.n_items) return;             // m_groups == 1: item == bx
   const int ridx = bx / (P.num_kv_heads / HPW);
   const int req = __builtin_amdgcn_readfirstlane(P.req_list ? P.req_list[ridx] : ridx);
   const int q_len = __builtin_amdgcn_readfirstlane(P.query_start_loc[req + 1] - P.query_start_loc[req]);
   if (q_len * (P.num_q_heads / P.num_kv_heads) <= 16)
-    verify_attn_body<1, HPW, KV8, NW, HD>(P, v_lds_raw, bx, by);
+    verify_attn_body<1, HPW, KV8, NW, HD, E>(P, v_lds_raw, bx, by);
   else
-    verify_attn_body<2, HPW, KV8, NW, HD>(P, v_lds_raw, bx, by);
+    verify_attn_body<2, HPW, KV8, NW, HD, E>(P, v_lds_raw, bx, by);
 }
 
 // MTQ = 0: the per-workgroup choice above
-template <int MTQ, int HPW, bool KV8, int NW = 4, int HD = kD>
+template <int MTQ, int HPW, bool KV8, int NW = 4, int HD = kD, typename E = ElemBf16>
 __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((MTQ == 1 && NW == 4) ? 3 : 2, (MTQ == 1 && NW == 4) ? 3 : 2))) verify_attn_kernel(AttnParams P) {
   __shared__ uint4 v_lds_raw[ShortLds<MTQ == 0 ? 2 : MTQ, NW, HD>::kU4];
   if constexpr (MTQ == 0)
-    verify_attn_body_dual<HPW, KV8, NW, HD>(P, v_lds_raw, blockIdx.x, blockIdx.y);
+    verify_attn_body_dual<HPW, KV8, NW, HD, E>(P, v_lds_raw, blockIdx.x, blockIdx.y);
   else
-    verify_attn_body<MTQ, HPW, KV8, NW, HD>(P, v_lds_raw, blockIdx.x, blockIdx.y);
+    verify_attn_body<MTQ, HPW, KV8, NW, HD, E>(P, v_lds_raw, blockIdx.x, blockIdx.y);
 }
 
 // One 32-token KV tile (K and V images in LDS at kb / vb, v_tile_off layout) against the NT row tiles of a wave
@@ -692,7 +694,7 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((M
 // the PV MFMAs.  Straight-line code: with one soft-max call per row tile the calls' branches kept the MFMA
 // chains and the VALU work of different row tiles from overlapping, and the wave (alone on its SIMD) ran at the
 // sum of every latency.
-template <int NT, int RT, int D, bool TR, int NP, typename Dma>
+template <int NT, int RT, int D, bool TR, int NP, typename E, typename Dma>
 __device__ __forceinline__ void long_tile_compute(unsigned ka0, unsigned va0, unsigned slot_off,
                                                   const uint4 (&qf)[RT][D / 32],
                                                   const bool (&row_ok)[RT], const int (&row_pos)[RT],
@@ -733,8 +735,8 @@ __device__ __forceinline__ void long_tile_compute(unsigned ka0, unsigned va0, un
       for (int mt = 0; mt < NT; ++mt)
 #pragma unroll
         for (int th = 0; th < 2; ++th)
-          st[mt][th] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kf[th][s]),
-                                                               __builtin_bit_cast(bf16x8, qf[mt][s]), st[mt][th], 0, 0, 0);
+          st[mt][th] = E::mfma(__builtin_bit_cast(typename E::vec8, kf[th][s]),
+                               __builtin_bit_cast(typename E::vec8, qf[mt][s]), st[mt][th]);
     if constexpr (TR) {
       const uint64_t c1 = __builtin_amdgcn_s_memtime();
       cyc[1] += c1 - c0;
@@ -789,7 +791,7 @@ __device__ __forceinline__ void long_tile_compute(unsigned ka0, unsigned va0, un
     // (P as ONE bf16 operand with the row sum taken over the rounded weights — what kernels that feed P to the matrix unit
     // in the value dtype do — was measured: long-only B=16 x 33 134 -> 103 us together with two workgroups per CU, but a
     // 40-token context then misses the 1e-3 tolerance: few terms, nothing averages the 2^-9 weight errors out.)
-    bf16x8 pfrag[NT], pfrag_lo[NT];
+    typename E::vec8 pfrag[NT], pfrag_lo[NT];
 #pragma unroll
     for (int mt = 0; mt < NT; ++mt) {
       // pieces i with i * (NT + 1) / NP == mt go out before this row tile's block, the rest after the last one.  Nothing
@@ -815,9 +817,11 @@ __device__ __forceinline__ void long_tile_compute(unsigned ka0, unsigned va0, un
       }
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        pfrag[mt][e] = static_cast<__bf16>(pv[e]);
-        pfrag_lo[mt][e] = static_cast<__bf16>(pv[e] - static_cast<float>(pfrag[mt][e]));
+        pfrag[mt][e] = E::head(pv[e]);
       }
+      E::pin(pfrag[mt]);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) pfrag_lo[mt][e] = E::tail(pv[e], pfrag[mt][e]);
     }
     if constexpr (NP > 0 && NT > 0) {
 #pragma unroll
@@ -842,11 +846,11 @@ __device__ __forceinline__ void long_tile_compute(unsigned ka0, unsigned va0, un
       const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(reinterpret_cast<lds_tr>(a + kHalf));
       typedef __attribute__((ext_vector_type(8))) short s16x8;
       const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-      const bf16x8 vfrag = __builtin_bit_cast(bf16x8, both);
+      const typename E::vec8 vfrag = __builtin_bit_cast(typename E::vec8, both);
 #pragma unroll
       for (int mt = 0; mt < NT; ++mt) {
-        o_acc[mt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfrag, pfrag[mt], o_acc[mt][dt], 0, 0, 0);
-        o_acc[mt][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vfrag, pfrag_lo[mt], o_acc[mt][dt], 0, 0, 0);
+        o_acc[mt][dt] = E::mfma(vfrag, pfrag[mt], o_acc[mt][dt]);
+        o_acc[mt][dt] = E::mfma(vfrag, pfrag_lo[mt], o_acc[mt][dt]);
       }
     }
     if constexpr (TR) cyc[3] += __builtin_amdgcn_s_memtime() - c0;
@@ -901,9 +905,10 @@ constexpr int kLong4LdsU4 = kLongRing * 2 * kTile * 16;
 // tile.  k_scale folds into the soft-max scale, v_scale into the output.
 // D = 64 (bf16 cache only): 128-byte rows, i.e. the DMA geometry of the fp8 case without the conversion (long drafts of a
 // head-size-64 model; requests of up to 32 rows take the streaming body's HD = 64 form).
-template <bool KV8, int D, bool TR = false>
+// E = the call's 16-bit element type (ElemBf16 | ElemF16): the images' type, "bf16" above, in an f16 call.
+template <bool KV8, int D, bool TR = false, typename E = ElemBf16>
 __device__ __forceinline__ void verify_attn_long4_body(const AttnParams& P, uint4* lds, const int bx, const int by, const int bz) {
-  static_assert(D == 128 || (D == 64 && !KV8), "head size 128, or 64 with a bf16 cache");
+  static_assert(D == 128 || (D == 64 && !KV8), "head size 128, or 64 with a 16-bit cache");
   uint64_t cyc[6] = {0, 0, 0, 0, 0, 0};   // TR: [0] issuing the next tile's DMA, [1..3] long_tile_compute, [4] vmcnt wait, [5] barrier
   uint64_t c_entry = 0, rt_entry = 0;
   if constexpr (TR) {
@@ -1177,10 +1182,10 @@ __device__ __forceinline__ void verify_attn_long4_body(const AttnParams& P, uint
     const uint4 v8 = *reinterpret_cast<const uint4*>(raw + kRawSlot / 2);
     char* kb = lds_b + kImgBase + (jt & 1) * (2 * kImg);
     char* vb = kb + kImg;
-    *reinterpret_cast<bf16x8*>(kb + tile_off<D>(tk, 2 * ch)) = fp8x8_to_bf16x8(k8.x, k8.y);
-    *reinterpret_cast<bf16x8*>(kb + tile_off<D>(tk, 2 * ch + 1)) = fp8x8_to_bf16x8(k8.z, k8.w);
-    *reinterpret_cast<bf16x8*>(vb + tile_off<D>(tk, 2 * ch)) = fp8x8_to_bf16x8(v8.x, v8.y);
-    *reinterpret_cast<bf16x8*>(vb + tile_off<D>(tk, 2 * ch + 1)) = fp8x8_to_bf16x8(v8.z, v8.w);
+    *reinterpret_cast<typename E::vec8*>(kb + tile_off<D>(tk, 2 * ch)) = E::from_fp8(k8.x, k8.y);
+    *reinterpret_cast<typename E::vec8*>(kb + tile_off<D>(tk, 2 * ch + 1)) = E::from_fp8(k8.z, k8.w);
+    *reinterpret_cast<typename E::vec8*>(vb + tile_off<D>(tk, 2 * ch)) = E::from_fp8(v8.x, v8.y);
+    *reinterpret_cast<typename E::vec8*>(vb + tile_off<D>(tk, 2 * ch + 1)) = E::from_fp8(v8.z, v8.w);
   };
   // wait until at most `tiles` of this wave's most recent tile loads are still in flight (DMAs retire in order); a tile is
   // my_pieces instructions of this wave (0, 2, 4, 5, 6 or 8)
@@ -1280,7 +1285,7 @@ __device__ __forceinline__ void verify_attn_long4_body(const AttnParams& P, uint
       auto dma = [&](int i) {
         if constexpr (!KV8) piece(i);   // (fp8: the tile's DMA went out at the loop head, before the conversion)
       };
-      long_tile_compute<NT, RT, D, TR, KV8 ? 0 : NPT>(ka0, va0, slot_off, qf, row_ok, row_pos, m_run, m_use, thr, l_run, o_acc,
+      long_tile_compute<NT, RT, D, TR, KV8 ? 0 : NPT, E>(ka0, va0, slot_off, qf, row_ok, row_pos, m_run, m_use, thr, l_run, o_acc,
                                                        t_begin + it * kTile, t_end, ctx, q_len, wnd, scale_log2, inv_scale,
                                                        g, c16, dma, cyc);
     }
@@ -1365,10 +1370,10 @@ __device__ __forceinline__ void verify_attn_long4_body(const AttnParams& P, uint
   }
 }
 
-template <bool KV8, int D = 128, bool TR = false>
+template <bool KV8, int D = 128, bool TR = false, typename E = ElemBf16>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) verify_attn_long4_kernel(AttnParams P) {
   __shared__ __attribute__((aligned(1024))) uint4 lds[kLong4LdsU4];
-  verify_attn_long4_body<KV8, D, TR>(P, lds, blockIdx.x, blockIdx.y, blockIdx.z);
+  verify_attn_long4_body<KV8, D, TR, E>(P, lds, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
 // Short requests and long drafts of one call in ONE launch: workgroups [0, n_long_wg) run the long-draft body,
@@ -1377,7 +1382,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
 // workgroups still sit beside the short ones on the CUs (both bodies are 4 waves, <= 256 VGPRs, 64 KiB LDS: two
 // workgroups per CU), and they come first in the grid so that they are placed before the CUs fill up.
 // The long part is padded to a multiple of 8 workgroups (idle ones), which keeps the short body's XCD-aware item mapping.
-template <int HPW, bool KV8, int MTQ, bool TR = false>
+template <int HPW, bool KV8, int MTQ, bool TR = false, typename E = ElemBf16>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
 verify_attn_pair_kernel(AttnParams PS, AttnParams PL, int n_long_wg, int n_long_pad, int long_x, int long_y, int short_x) {
   constexpr int kShortU4 = ShortLds<MTQ == 0 ? 2 : MTQ, 4>::kU4;
@@ -1389,15 +1394,15 @@ verify_attn_pair_kernel(AttnParams PS, AttnParams PL, int n_long_wg, int n_long_
     if (b < n_long_wg) {
       const int x = b % long_x, yz = b / long_x;
       const int y = yz % long_y, z = yz / long_y;
-      verify_attn_long4_body<KV8, 128, TR>(PL, lds, x, y, z);   // (TR: the diagnostic cycle account, tools/microbench.py mixphases)
+      verify_attn_long4_body<KV8, 128, TR, E>(PL, lds, x, y, z);   // (TR: the diagnostic cycle account, tools/microbench.py mixphases)
     }
   } else {
     const int sb = b - n_long_pad;
     __builtin_amdgcn_s_setprio(3);   // the memory-bound short body sets the launch's end: its waves issue first
     if constexpr (MTQ == 0)
-      verify_attn_body_dual<HPW, KV8, 4>(PS, lds, sb % short_x, sb / short_x);
+      verify_attn_body_dual<HPW, KV8, 4, kD, E>(PS, lds, sb % short_x, sb / short_x);
     else
-      verify_attn_body<MTQ, HPW, KV8, 4>(PS, lds, sb % short_x, sb / short_x);
+      verify_attn_body<MTQ, HPW, KV8, 4, kD, E>(PS, lds, sb % short_x, sb / short_x);
   }
   if (PS.trace) {
     __syncthreads();
@@ -1420,7 +1425,7 @@ verify_attn_pair_kernel(AttnParams PS, AttnParams PL, int n_long_wg, int n_long_
 // r03: requesting the first four slots' values together with the {max, sum} pairs — one memory round trip per row instead
 // of two — left the launch at 4.85 us (rocprofv3, bench); two to four rows per wave with every phase issued for all of them
 // (a grid of about one workgroup per CU) took 5.2 / 9.8 / 11.2 us: one row per wave it stays.)
-template <int D>
+template <int D, typename E = ElemBf16>
 __global__ void __launch_bounds__(256)
 verify_attn_combine_kernel(const float* __restrict__ ws_o, const float* __restrict__ ws_ml, int n_parts, int total_rows,
                            int num_q_heads, uint16_t* __restrict__ out, int64_t out_stride) {
@@ -1480,7 +1485,7 @@ verify_attn_combine_kernel(const float* __restrict__ ws_o, const float* __restri
   if (!(L > 0.0f)) acc0 = acc1 = 0.0f;  // a row with nothing visible (cannot happen for a real token): zeros
   const int tok = row / num_q_heads, head = row - tok * num_q_heads;
   uint16_t* op = out + static_cast<int64_t>(tok) * out_stride + static_cast<int64_t>(head) * D + 2 * lane;
-  const uint32_t packed = static_cast<uint32_t>(f32_to_bf16(acc0 * inv)) | (static_cast<uint32_t>(f32_to_bf16(acc1 * inv)) << 16);
+  const uint32_t packed = static_cast<uint32_t>(E::round(acc0 * inv)) | (static_cast<uint32_t>(E::round(acc1 * inv)) << 16);
   if (D == 128 || 2 * lane < D) *reinterpret_cast<uint32_t*>(op) = packed;
 }
 
@@ -1714,10 +1719,31 @@ int aic_verify_attention_win(const void* q, int64_t q_stride, const void* k_cach
                              const int32_t* block_table, int max_blocks_per_seq, const int32_t* seq_lens,
                              const int32_t* query_start_loc, int batch, int num_tokens, int max_q_len, int num_q_heads,
                              int num_kv_heads, int head_size, int block_size, float sm_scale, void* out,
-                             int64_t out_stride, void* workspace, size_t workspace_bytes, int max_seq_len_full,
+                             int64_t out_stride, void* workspace, size_t workspace_bytes, int max_seq_len,
                              const int32_t* short_reqs, int n_short, const int32_t* long_reqs, int n_long,
                              int sliding_window, const float* sinks, void* stream) {
-  if (batch == 0 || num_tokens == 0) return AIC_OK;
+  return aic_verify_attention_dt(q, q_stride, k_cache, v_cache, block_stride, kv_dtype, k_scale, v_scale, block_table,
+                                 max_blocks_per_seq, seq_lens, query_start_loc, batch, num_tokens, max_q_len, num_q_heads,
+                                 num_kv_heads, head_size, block_size, sm_scale, out, out_stride, workspace, workspace_bytes,
+                                 max_seq_len, short_reqs, n_short, long_reqs, n_long, sliding_window, sinks, AIC_DT_BF16,
+                                 stream);
+}
+
+}  // extern "C"
+
+// The call for element type E (ElemBf16 | ElemF16: q, out and a 16-bit cache); kv8 = the cache holds e4m3 bytes.  The
+// launch logic is the same for both types — the f16 bodies keep the resource bounds it assumes —
+// and the diagnostic instantiations (cycle accounts of the long-draft body) exist for bf16 only.
+template <typename E>
+static int verify_attention_impl(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache,
+                                 int64_t block_stride, const bool kv8, const float* k_scale, const float* v_scale,
+                                 const int32_t* block_table, int max_blocks_per_seq, const int32_t* seq_lens,
+                                 const int32_t* query_start_loc, int batch, int num_tokens, int max_q_len, int num_q_heads,
+                                 int num_kv_heads, int head_size, int block_size, float sm_scale, void* out,
+                                 int64_t out_stride, void* workspace, size_t workspace_bytes, int max_seq_len_full,
+                                 const int32_t* short_reqs, int n_short, const int32_t* long_reqs, int n_long,
+                                 int sliding_window, const float* sinks, void* stream) {
+  constexpr bool kTraceable = std::is_same<E, ElemBf16>::value;
   AIC_REQUIRE(sliding_window >= 0, "sliding_window must be >= 0 (0 = none)");
   // what a request streams at most: the whole context, or — sliding window — the window plus the draft and tile slack
   const int max_seq_len = sliding_window > 0 ? std::min(max_seq_len_full, sliding_window + max_q_len + kTile) : max_seq_len_full;
@@ -1732,18 +1758,13 @@ int aic_verify_attention_win(const void* q, int64_t q_stride, const void* k_cach
                                (n_short == 0 || short_reqs) && (n_long == 0 || long_reqs)),
               "short/long request lists must partition the batch");
   if (head_size != kD && head_size != 64) {
-    set_error("head_size %d not supported (128, or 64 with a bf16 cache)", head_size);
+    set_error("head_size %d not supported (128, or 64 with a 16-bit cache)", head_size);
     return AIC_ERR_UNSUPPORTED;
   }
-  if (head_size == 64 && kv_dtype != AIC_DT_BF16) {
-    set_error("head_size 64 needs a bf16 kv cache");
+  if (head_size == 64 && kv8) {
+    set_error("head_size 64 needs a 16-bit kv cache");
     return AIC_ERR_UNSUPPORTED;
   }
-  if (kv_dtype != AIC_DT_BF16 && kv_dtype != AIC_DT_FP8_E4M3) {
-    set_error("kv cache dtype %d not supported (bf16 or fp8 e4m3)", kv_dtype);
-    return AIC_ERR_UNSUPPORTED;
-  }
-  const bool kv8 = kv_dtype == AIC_DT_FP8_E4M3;
   AIC_REQUIRE(!kv8 || (k_scale && v_scale), "an fp8 kv cache needs k_scale and v_scale (device scalars)");
   AIC_REQUIRE(q_stride % 8 == 0 && out_stride % 2 == 0 && block_stride % 16 == 0, "strides must keep 16-byte alignment");
   if (block_size % 16 != 0) {
@@ -1752,7 +1773,7 @@ int aic_verify_attention_win(const void* q, int64_t q_stride, const void* k_cach
   }
   AIC_NEED_DEVICE();
 
-  const bool d64 = head_size == 64;   // the secondary head size (gpt-oss; bf16 cache only)
+  const bool d64 = head_size == 64;   // the secondary head size (gpt-oss; 16-bit cache only)
   const int G = num_q_heads / num_kv_heads;
   const int max_rows = max_q_len * G;
   const bool wave_heads = num_kv_heads % 4 == 0;
@@ -1860,11 +1881,11 @@ int aic_verify_attention_win(const void* q, int64_t q_stride, const void* k_cach
   auto launch_short = [&](int mtq_, int hpw_, dim3 grid_) {
 #define AIC_SHORT(MTQ_, HPW_)                                                                  \
   if (d64)                                                                                     \
-    launch(verify_attn_kernel<MTQ_, HPW_, false, 4, 64>, grid_, dim3(256), s, P);                  \
+    launch(verify_attn_kernel<MTQ_, HPW_, false, 4, 64, E>, grid_, dim3(256), s, P);           \
   else if (kv8)                                                                                \
-    launch(verify_attn_kernel<MTQ_, HPW_, true>, grid_, dim3(256), s, P);                      \
+    launch(verify_attn_kernel<MTQ_, HPW_, true, 4, kD, E>, grid_, dim3(256), s, P);            \
   else                                                                                         \
-    launch(verify_attn_kernel<MTQ_, HPW_, false>, grid_, dim3(256), s, P);
+    launch(verify_attn_kernel<MTQ_, HPW_, false, 4, kD, E>, grid_, dim3(256), s, P);
     if (mtq_ == 0) {
       if (hpw_ == 4) { AIC_SHORT(0, 4) } else if (hpw_ == 2) { AIC_SHORT(0, 2) } else { AIC_SHORT(0, 1) }
     } else if (mtq_ == 1) {
@@ -1939,12 +1960,18 @@ int aic_verify_attention_win(const void* q, int64_t q_stride, const void* k_cach
       const dim3 pgrid(static_cast<unsigned>(n_long_pad + short_wg));
       P.trace = (g_attn_trace && static_cast<int>(pgrid.x) <= g_attn_trace_cap) ? g_attn_trace : nullptr;
 #define AIC_PAIR_LAUNCH(HPW_, KV8_)                                                                             \
-  launch(verify_attn_pair_kernel<HPW_, KV8_, 0>, pgrid, dim3(256), s, P, PL, n_long_wg, n_long_pad, long_x, n_splits_long, short_x);
-      if (g_attn_ptrace && hpw == 4 && !kv8 && n_long_wg * 8 <= g_attn_ptrace_cap && long_x < 65536) {
-        // debug: the long workgroups of a MIXED call keep the per-wave cycle account (tools/microbench.py mixphases)
-        PL.ptrace = g_attn_ptrace;
-        PL.ptrace_stride = long_x | (n_splits_long << 16);
-        launch(verify_attn_pair_kernel<4, false, 0, true>, pgrid, dim3(256), s, P, PL, n_long_wg, n_long_pad, long_x, n_splits_long, short_x);
+  launch(verify_attn_pair_kernel<HPW_, KV8_, 0, false, E>, pgrid, dim3(256), s, P, PL, n_long_wg, n_long_pad, long_x, n_splits_long, short_x);
+      bool traced = false;
+      if constexpr (kTraceable) {
+        if (g_attn_ptrace && hpw == 4 && !kv8 && n_long_wg * 8 <= g_attn_ptrace_cap && long_x < 65536) {
+          // debug: the long workgroups of a MIXED call keep the per-wave cycle account (tools/microbench.py mixphases)
+          PL.ptrace = g_attn_ptrace;
+          PL.ptrace_stride = long_x | (n_splits_long << 16);
+          launch(verify_attn_pair_kernel<4, false, 0, true>, pgrid, dim3(256), s, P, PL, n_long_wg, n_long_pad, long_x, n_splits_long, short_x);
+          traced = true;
+        }
+      }
+      if (traced) {
       } else if (hpw == 4) {
         if (kv8) { AIC_PAIR_LAUNCH(4, true) } else { AIC_PAIR_LAUNCH(4, false) }
       } else if (hpw == 2) {
@@ -1975,16 +2002,22 @@ int aic_verify_attention_win(const void* q, int64_t q_stride, const void* k_cach
       const int per_block_rows = 4 * kLongTilesPerWave * 16;
       PL.n_splits = n_splits_long;
       dim3 grid(static_cast<unsigned>(n_long * num_kv_heads), n_splits_long, (max_rows + per_block_rows - 1) / per_block_rows);
-      if (g_attn_ptrace && !d64 && !kv8 && n_short == 0 && static_cast<int>(grid.x * grid.y * grid.z) * 8 <= g_attn_ptrace_cap) {
-        PL.ptrace = g_attn_ptrace;   // debug: per-wave cycle accounting of a long-only call (tools/microbench.py longphases)
-        PL.ptrace_stride = static_cast<int>(grid.x) | (static_cast<int>(grid.y) << 16);
-        launch(verify_attn_long4_kernel<false, 128, true>, grid, dim3(256), s, PL);
+      bool traced = false;
+      if constexpr (kTraceable) {
+        if (g_attn_ptrace && !d64 && !kv8 && n_short == 0 && static_cast<int>(grid.x * grid.y * grid.z) * 8 <= g_attn_ptrace_cap) {
+          PL.ptrace = g_attn_ptrace;   // debug: per-wave cycle accounting of a long-only call (tools/microbench.py longphases)
+          PL.ptrace_stride = static_cast<int>(grid.x) | (static_cast<int>(grid.y) << 16);
+          launch(verify_attn_long4_kernel<false, 128, true>, grid, dim3(256), s, PL);
+          traced = true;
+        }
+      }
+      if (traced) {
       } else if (d64)
-        launch(verify_attn_long4_kernel<false, 64>, grid, dim3(256), overlap ? side->stream : s, PL);
+        launch(verify_attn_long4_kernel<false, 64, false, E>, grid, dim3(256), overlap ? side->stream : s, PL);
       else if (kv8)
-        launch(verify_attn_long4_kernel<true, 128>, grid, dim3(256), overlap ? side->stream : s, PL);
+        launch(verify_attn_long4_kernel<true, 128, false, E>, grid, dim3(256), overlap ? side->stream : s, PL);
       else
-        launch(verify_attn_long4_kernel<false, 128>, grid, dim3(256), overlap ? side->stream : s, PL);
+        launch(verify_attn_long4_kernel<false, 128, false, E>, grid, dim3(256), overlap ? side->stream : s, PL);
       if (overlap) AIC_HIP_TRY(hipEventRecord(side->join, side->stream));
       return AIC_OK;
     };
@@ -2008,12 +2041,40 @@ int aic_verify_attention_win(const void* q, int64_t q_stride, const void* k_cach
   if ((rc = launch_ok("verify_attn_kernel")) != AIC_OK) return rc;
   if (P.direct && !P.mark_final) return AIC_OK;   // every row of the call is already final: no combine launch
   if (d64)
-    launch(verify_attn_combine_kernel<64>, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), s, P.ws_o, P.ws_ml, n_parts_total,
+    launch(verify_attn_combine_kernel<64, E>, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), s, P.ws_o, P.ws_ml, n_parts_total,
            static_cast<int>(rows), num_q_heads, static_cast<uint16_t*>(out), out_stride);
   else
-    launch(verify_attn_combine_kernel<128>, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), s, P.ws_o, P.ws_ml, n_parts_total,
+    launch(verify_attn_combine_kernel<128, E>, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), s, P.ws_o, P.ws_ml, n_parts_total,
            static_cast<int>(rows), num_q_heads, static_cast<uint16_t*>(out), out_stride);
   return launch_ok("verify_attn_combine_kernel");
+}
+
+extern "C" {
+
+// One attention call per step whatever the model's dtype, as on the reference path (arctic_inference/vllm/ulysses.py:510):
+// q_dtype is the element type of q and of out; the dtype rules are answered before anything is launched.
+int aic_verify_attention_dt(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache,
+                            int64_t block_stride, int kv_dtype, const float* k_scale, const float* v_scale,
+                            const int32_t* block_table, int max_blocks_per_seq, const int32_t* seq_lens,
+                            const int32_t* query_start_loc, int batch, int num_tokens, int max_q_len, int num_q_heads,
+                            int num_kv_heads, int head_size, int block_size, float sm_scale, void* out,
+                            int64_t out_stride, void* workspace, size_t workspace_bytes, int max_seq_len,
+                            const int32_t* short_reqs, int n_short, const int32_t* long_reqs, int n_long,
+                            int sliding_window, const float* sinks, int q_dtype, void* stream) {
+  if (batch == 0 || num_tokens == 0) return AIC_OK;
+  if (const int rc = attn_check_dtypes(q_dtype, kv_dtype); rc != AIC_OK) return rc;
+  const bool kv8 = kv_dtype == AIC_DT_FP8_E4M3;
+  if (q_dtype == AIC_DT_F16)
+    return verify_attention_impl<ElemF16>(q, q_stride, k_cache, v_cache, block_stride, kv8, k_scale, v_scale, block_table,
+                                          max_blocks_per_seq, seq_lens, query_start_loc, batch, num_tokens, max_q_len,
+                                          num_q_heads, num_kv_heads, head_size, block_size, sm_scale, out, out_stride,
+                                          workspace, workspace_bytes, max_seq_len, short_reqs, n_short, long_reqs, n_long,
+                                          sliding_window, sinks, stream);
+  return verify_attention_impl<ElemBf16>(q, q_stride, k_cache, v_cache, block_stride, kv8, k_scale, v_scale, block_table,
+                                         max_blocks_per_seq, seq_lens, query_start_loc, batch, num_tokens, max_q_len,
+                                         num_q_heads, num_kv_heads, head_size, block_size, sm_scale, out, out_stride,
+                                         workspace, workspace_bytes, max_seq_len, short_reqs, n_short, long_reqs, n_long,
+                                         sliding_window, sinks, stream);
 }
 
 // ---- a run of layers as one graph launch ------------------------------------------------------------------------------

@@ -228,6 +228,24 @@ def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, exp_noise: Op
 # ------------------------------------------------------------------------------------------------
 # A5 verify attention
 # ------------------------------------------------------------------------------------------------
+_ATTN_Q_DTYPES = {torch.bfloat16: N.DT_BF16, torch.float16: N.DT_F16}
+
+
+def _attn_dtypes(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, out: Optional[torch.Tensor]):
+    """(q_dtype, kv_dtype) codes of an attention call, after the dtype rules of aic_verify_attention_dt: q is bf16 or
+    fp16, out has q's dtype, a 16-bit cache has q's dtype (else float8_e4m3fn).  ValueError before anything is launched."""
+    qd = _ATTN_Q_DTYPES.get(q.dtype)
+    if qd is None:
+        raise ValueError(f"attention serves bfloat16 and float16 queries, not {q.dtype}")
+    if out is not None and out.dtype != q.dtype:
+        raise ValueError(f"out must have the query's dtype ({q.dtype}), not {out.dtype}")
+    if k_cache.dtype != v_cache.dtype:
+        raise ValueError(f"key and value caches must share a dtype ({k_cache.dtype} / {v_cache.dtype})")
+    if k_cache.dtype in _ATTN_Q_DTYPES and k_cache.dtype != q.dtype:
+        raise ValueError(f"a 16-bit kv cache must have the query's dtype ({q.dtype}), not {k_cache.dtype}")
+    return qd, N.torch_dtype_code(k_cache.dtype)
+
+
 def verify_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor,
                      seq_lens: torch.Tensor, query_start_loc: torch.Tensor, max_q_len: int, max_seq_len: int,
                      sm_scale: float, out: Optional[torch.Tensor] = None, num_splits_max: int = 64,
@@ -235,12 +253,13 @@ def verify_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
                      k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None,
                      stream: Optional[int] = None, sliding_window: int = 0,
                      sinks: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """q [T, Hq, D] (token stride may exceed Hq*D: a view into an all-to-all receive buffer works),
-    caches [num_blocks, block_size, Hkv, D] in bf16, or float8_e4m3fn with per-tensor `k_scale` / `v_scale`
-    (device scalars, the scales A16 divided by); returns [T, Hq, D].  `q_lens_host` (the per-request query
+    """q [T, Hq, D] in bf16 or fp16 (token stride may exceed Hq*D: a view into an all-to-all receive buffer works),
+    caches [num_blocks, block_size, Hkv, D] in q's dtype, or float8_e4m3fn with per-tensor `k_scale` / `v_scale`
+    (device scalars, the scales A16 divided by); returns [T, Hq, D] in q's dtype (aic_verify_attention_dt).  `q_lens_host` (the per-request query
     lengths, which vLLM has on the host) lets long drafts take the shared-tile kernel.  `stream`: raw HIP stream
     handle (default: torch's current stream; a caller that issues one call per layer looks it up once).
-    `sliding_window` W > 0 / `sinks` f32 [Hq]: the per-layer features of gpt-oss-class models (aic_verify_attention_win)."""
+    `sliding_window` W > 0 / `sinks` f32 [Hq]: the per-layer features of gpt-oss-class models."""
+    qd, kvd = _attn_dtypes(q, k_cache, v_cache, out)
     _need_cuda(q, k_cache, v_cache, block_table, seq_lens, query_start_loc, sinks)
     if sinks is not None and (sinks.dtype != torch.float32 or sinks.numel() != q.shape[1] or not sinks.is_contiguous()):
         raise ValueError("sinks: contiguous float32, one value per query head")
@@ -252,28 +271,31 @@ def verify_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     B = seq_lens.numel()
     wsb = N.lib().aic_verify_attention_workspace_bytes(T, Hq, D, num_splits_max)
     ws = _workspace(wsb, q.device, stream)
-    kvd = N.torch_dtype_code(k_cache.dtype)
     if req_split is None and q_lens_host is not None:
         req_split = split_requests(q_lens_host, Hq // Hkv, q.device)
     short, n_short, long_, n_long = req_split if req_split is not None else (None, 0, None, 0)
-    N.check(N.lib().aic_verify_attention_win(
+    N.check(N.lib().aic_verify_attention_dt(
         q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(0), kvd, _ptr(k_scale),
         _ptr(v_scale), block_table.data_ptr(), block_table.size(1), seq_lens.data_ptr(), query_start_loc.data_ptr(), B, T,
         int(max_q_len), Hq, Hkv, D, bs, float(sm_scale), out.data_ptr(), out.stride(0), ws.data_ptr(), ws.numel(),
         int(max_seq_len), _ptr(short) if n_short else None, n_short, _ptr(long_) if n_long else None, n_long,
-        int(sliding_window or 0), _ptr(sinks), N.current_stream_ptr() if stream is None else stream))
+        int(sliding_window or 0), _ptr(sinks), qd, N.current_stream_ptr() if stream is None else stream))
     return out
 
 
 class VerifyAttentionPlan:
     """verify_attention for a caller that issues one call per layer with only the cache pointers changing (every layer
     of a step shares the batch geometry): argument checks, workspace sizing and the ctypes argument list are built once
-    per step, `run(k_cache, v_cache)` is one foreign call.  Same semantics as verify_attention()."""
+    per step, `run(k_cache, v_cache)` is one foreign call.  Same semantics as verify_attention(), for bf16 only (the
+    stand-alone engine's dtype: aic_verify_attention_ex / aic_verify_attention_layers carry no query dtype)."""
 
     def __init__(self, q: torch.Tensor, out: torch.Tensor, kv_like: torch.Tensor, block_table: torch.Tensor,
                  seq_lens: torch.Tensor, query_start_loc: torch.Tensor, max_q_len: int, max_seq_len: int, sm_scale: float,
                  req_split=None, k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None,
                  num_splits_max: int = 64, stream: Optional[int] = None):
+        if q.dtype != torch.bfloat16 or out.dtype != torch.bfloat16 or kv_like.dtype == torch.float16:
+            raise ValueError("VerifyAttentionPlan serves bfloat16 queries and outputs with a bfloat16 or fp8 cache "
+                             f"(got q {q.dtype}, out {out.dtype}, cache {kv_like.dtype}); fp16 models call verify_attention()")
         _need_cuda(q, out, kv_like, block_table, seq_lens, query_start_loc)
         T, Hq, D = q.shape
         nb, bs, Hkv, D2 = kv_like.shape
@@ -402,12 +424,13 @@ def step_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor
                    k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None,
                    stream: Optional[int] = None, sliding_window: int = 0,
                    sinks: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Attention for a whole step whatever its query lengths (aic_step_attention_win): prefill chunks (q_len > 33)
-    beside decodes and long drafts, in any batch order.  Same tensors and conventions as verify_attention; the step's
+    """Attention for a whole step whatever its query lengths (aic_step_attention_dt): prefill chunks (q_len > 33)
+    beside decodes and long drafts, in any batch order.  Same tensors, dtypes and conventions as verify_attention; the step's
     geometry comes from `q_lens_host` or a StepSplit built from it once per step (pass that to every layer).
     `sliding_window` W > 0 / `sinks` f32 [Hq]: the per-layer features of gpt-oss-class models, as in verify_attention."""
     if sinks is not None and (sinks.dtype != torch.float32 or sinks.numel() != q.shape[1] or not sinks.is_contiguous()):
         raise ValueError("sinks: contiguous float32, one value per query head")
+    qd, kvd = _attn_dtypes(q, k_cache, v_cache, out)
     _need_cuda(q, k_cache, v_cache, block_table, seq_lens, query_start_loc, sinks)
     T, Hq, D = q.shape
     nb, bs, Hkv, D2 = k_cache.shape
@@ -424,14 +447,14 @@ def step_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor
     wsb = N.lib().aic_step_attention_workspace_bytes(sp.num_decode_tokens, sp.n_prefill, sp.max_prefill_q_len, Hq, Hkv, D,
                                                      num_splits_max)
     ws = _workspace(wsb, q.device, stream)
-    N.check(N.lib().aic_step_attention_win(
+    N.check(N.lib().aic_step_attention_dt(
         q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(0),
-        N.torch_dtype_code(k_cache.dtype), _ptr(k_scale), _ptr(v_scale), block_table.data_ptr(), block_table.size(1),
+        kvd, _ptr(k_scale), _ptr(v_scale), block_table.data_ptr(), block_table.size(1),
         seq_lens.data_ptr(), query_start_loc.data_ptr(), sp.batch, sp.num_tokens, Hq, Hkv, D, bs, float(sm_scale),
         out.data_ptr(), out.stride(0), ws.data_ptr(), ws.numel(), int(max_seq_len), sp.req_lists.data_ptr(), sp.n_short,
         sp.n_prefill, sp.n_long, sp.decode_qsl.data_ptr(), _ptr(sp.decode_index) if sp.num_decode_tokens else None,
         sp.num_decode_tokens, max(1, sp.max_decode_q_len), sp.max_prefill_q_len, int(sliding_window or 0), _ptr(sinks),
-        N.current_stream_ptr() if stream is None else stream))
+        qd, N.current_stream_ptr() if stream is None else stream))
     return out
 
 

@@ -86,7 +86,7 @@ def route(max_query_len: int, q_lens, batch: int, prefill_on: bool, layer_ok: bo
     """Which attention serves a call: "verify" (every request has at most MAX_SPEC_LEN + 1 query tokens: the verify
     bodies, as before), "step" (prefill chunks in the step, served by aic_step_attention) or "fallback" (vLLM's
     backend).  Prefill steps take the HIP route only with the switch on, on a layer the prefill body serves (head size
-    128 with a bf16 / fp8 cache, or 64 with a bf16 cache; any sliding window, sinks or none; the caller has already
+    128 with a 16-bit / fp8 cache, or 64 with a 16-bit cache; any sliding window, sinks or none; the caller has already
     sent alibi and soft-cap layers back), with published q_lens that describe the call
     (`batch` requests, the longest `max_query_len` tokens) and outside graph capture."""
     from .runner_logic import MAX_SPEC_LEN

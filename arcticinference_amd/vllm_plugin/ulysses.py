@@ -230,9 +230,9 @@ def build_ulysses_patches():
         # -- the verify-attention route -------------------------------------------------------------
         def _arctic_verify(self, query, key, value):
             """Decode / verify steps on the HIP kernel: K/V of the step's tokens go into the paged cache
-            (aic_reshape_and_cache_flash_bulk, one layer), then aic_verify_attention_ex reads the cache once for all
+            (aic_reshape_and_cache_flash_bulk, one layer), then aic_verify_attention_dt reads the cache once for all
             draft positions of a request.  Returns None when the step is not one this kernel serves (prefill chunks,
-            another cache layout, no metadata): the caller then uses vLLM's backend."""
+            another cache layout, a dtype other than bf16 / fp16, no metadata): the caller then uses vLLM's backend."""
             if not query.is_cuda:
                 return None
             # Full-graph capture (vLLM's full_cuda_graph; its default piecewise graphs cut at this op and never get here):
@@ -264,8 +264,12 @@ def build_ulysses_patches():
             fp8 = kv_cache.dtype in (torch.uint8, torch.float8_e4m3fn)
             if fp8 and self.head_size != 128:
                 return None
-            # steps with prefill chunks (ARCTIC_INFERENCE_HIP_PREFILL): aic_step_attention_win, on layers its prefill body
-            # serves (head size 128, or 64 with a bf16 cache; any window, sinks or none)
+            # the kernels are instantiated for bf16 and fp16 models (aic_verify_attention_dt); a 16-bit cache has the
+            # query's type.  Anything else (a float32 model, a cache of the other 16-bit type) is vLLM's backend's.
+            if query.dtype not in (torch.bfloat16, torch.float16) or (not fp8 and kv_cache.dtype != query.dtype):
+                return None
+            # steps with prefill chunks (ARCTIC_INFERENCE_HIP_PREFILL): aic_step_attention_dt, on layers its prefill body
+            # serves (head size 128, or 64 with a 16-bit cache; any window, sinks or none)
             route = step_context.route(max_q, step_context.q_lens(), meta.seq_lens.numel(), step_context.prefill_on(),
                                        self.head_size == 128 or (self.head_size == 64 and not fp8), capturing)
             if route == "fallback":

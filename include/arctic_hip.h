@@ -425,11 +425,11 @@ int aic_lstm_head(aic_lstm* m, int head_index, const int32_t* last_tokens /* [B]
  *     (FlashAttention cache layout [num_blocks, block_size, Hkv, D], llama_swiftkv.py:617), new
  *     K/V already written.  Linear chains only (model_runner.py:734-740): the "tree" mask is
  *     causal within the chunk.
- *       q/out: bf16 [T][Hq][D] (token stride q_stride / out_stride elements)
+ *       q/out: bf16 [T][Hq][D] (token stride q_stride / out_stride elements); f16 through aic_verify_attention_dt
  *       block_table int32 [B][max_blocks]; seq_lens int32 [B] (context incl. the new tokens);
- *       query_start_loc int32 [B+1].  head_size 128, or 64 with a bf16 cache (anything else:
- *       AIC_ERR_UNSUPPORTED); block_size a multiple of 16.  kv_dtype BF16 or FP8_E4M3 (+ k_scale / v_scale
- *       device scalars).
+ *       query_start_loc int32 [B+1].  head_size 128, or 64 with a 16-bit cache (anything else:
+ *       AIC_ERR_UNSUPPORTED); block_size a multiple of 16.  kv_dtype BF16 (F16 for an f16 query, through
+ *       aic_verify_attention_dt) or FP8_E4M3 (+ k_scale / v_scale device scalars).
  *     workspace >= aic_verify_attention_workspace_bytes(...), private to the call until it completes on
  *     `stream`.  Graph-capture safe: this entry point (no host-side request lists) is the form the vLLM
  *     route records under a capturing stream — batch, num_tokens, max_q_len and max_seq_len are then upper
@@ -476,10 +476,27 @@ int aic_verify_attention_win(const void* q, int64_t q_stride, const void* k_cach
                              void* out, int64_t out_stride, void* workspace, size_t workspace_bytes,
                              int max_seq_len, const int32_t* short_reqs, int n_short, const int32_t* long_reqs,
                              int n_long, int sliding_window, const float* sinks, void* stream);
+/* The same for a model of either 16-bit type.  The reference sends every step of every dtype through one attention call
+ * (ulysses.py:510), and vLLM runs AWQ / GPTQ checkpoints and `--dtype half` in float16.
+ *   q_dtype: AIC_DT_BF16 or AIC_DT_F16, the element type of q AND of out;
+ *   kv_dtype: q_dtype (a 16-bit cache has the query's type) or AIC_DT_FP8_E4M3.
+ * Anything else is AIC_ERR_UNSUPPORTED, answered before any launch; head_size 64 needs a 16-bit cache as before.  An f16
+ * call takes the same bodies instantiated for f16: f16 MFMAs, an exact e4m3 -> f16 tile conversion, P as an f16 head +
+ * tail, the output rounded to nearest even.  Every entry point above is this one with q_dtype = AIC_DT_BF16:
+ * aic_verify_attention_win(...) == aic_verify_attention_dt(..., sliding_window, sinks, AIC_DT_BF16, stream). */
+int aic_verify_attention_dt(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache,
+                            int64_t block_stride, int kv_dtype, const float* k_scale, const float* v_scale,
+                            const int32_t* block_table, int max_blocks_per_seq, const int32_t* seq_lens,
+                            const int32_t* query_start_loc, int batch, int num_tokens, int max_q_len,
+                            int num_q_heads, int num_kv_heads, int head_size, int block_size, float sm_scale,
+                            void* out, int64_t out_stride, void* workspace, size_t workspace_bytes,
+                            int max_seq_len, const int32_t* short_reqs, int n_short, const int32_t* long_reqs,
+                            int n_long, int sliding_window, const float* sinks, int q_dtype, void* stream);
 /* aic_verify_attention_ex for `n_layers` layers of one engine step in one call: k_caches / v_caches are HOST arrays of
  * device pointers (one cache pair per layer, same shape / dtype / strides), q and out advance by *_layer_stride elements
  * per layer (0: shared).  For drivers that own the whole step (arcticinference_amd/engine.py); inside vLLM attention is
- * called per layer. */
+ * called per layer.  bf16 only (q, out and a 16-bit cache), like the stand-alone engine that uses it: there is no q_dtype
+ * here, and a kv_dtype other than AIC_DT_BF16 / AIC_DT_FP8_E4M3 is AIC_ERR_UNSUPPORTED. */
 int aic_verify_attention_layers(const void* q, int64_t q_stride, int64_t q_layer_stride, const void* const* k_caches /*host*/,
                                 const void* const* v_caches /*host*/, int n_layers, int64_t block_stride, int kv_dtype,
                                 const float* k_scale, const float* v_scale, const int32_t* block_table,
@@ -493,7 +510,7 @@ int aic_verify_attention_layers(const void* q, int64_t q_stride, int64_t q_layer
  * A5p  Whole-step attention with prefill chunks — what `self._orig_forward(q_, k_, v_)` reaches through vLLM's attention
  *      backend for ANY step (ulysses.py:510): decodes, long drafts and prefill chunks (q_len > 33, chunked prefill and
  *      the Ulysses SP prefill) in one call.  Same semantics, layouts and cache dtypes as aic_verify_attention; the
- *      prefill part needs head_size 128 (or 64 with a bf16 cache) and at most 8 query heads per kv head.
+ *      prefill part needs head_size 128 (or 64 with a 16-bit cache) and at most 8 query heads per kv head.
  *        req_lists: device int32[batch] = the short requests (n_short, q_len * Hq/Hkv <= 32 rows), then the prefill
  *            requests (n_prefill), then the long drafts (n_long); together a partition of the batch, in any order of
  *            the batch (ops.split_order3).
@@ -525,7 +542,7 @@ int aic_step_attention(const void* q, int64_t q_stride, const void* k_cache, con
  * included, ulysses.py:510):
  *   sliding_window W > 0: query position p attends keys p - W + 1 .. p only (0: the whole context);
  *   sinks: device f32 [num_q_heads] (NULL: none), one extra soft-max logit per head, not multiplied by sm_scale.
- * The prefill body then serves head_size 128 (bf16 or fp8 cache) or head_size 64 (bf16 cache only; AIC_ERR_UNSUPPORTED
+ * The prefill body then serves head_size 128 (16-bit or fp8 cache) or head_size 64 (16-bit cache only; AIC_ERR_UNSUPPORTED
  * otherwise); the decode part of a mixed step goes through aic_verify_attention_win with the same window and sinks.
  * The workspace query above is an upper bound for every window and sink setting.
  * aic_step_attention(...) == aic_step_attention_win(..., 0, NULL, stream). */
@@ -538,6 +555,20 @@ int aic_step_attention_win(const void* q, int64_t q_stride, const void* k_cache,
                            const int32_t* decode_query_start_loc, const int32_t* decode_token_index,
                            int num_decode_tokens, int max_decode_q_len, int max_prefill_q_len, int sliding_window,
                            const float* sinks, void* stream);
+/* The same for a model of either 16-bit type (one attention call per step whatever the dtype, ulysses.py:510): q_dtype
+ * and kv_dtype as in aic_verify_attention_dt, checked before any launch; the gather / scatter of a mixed step's decode
+ * rows moves 2-byte elements whatever they mean, the decode part goes through aic_verify_attention_dt and the prefill
+ * body is instantiated for f16 like the verify bodies.
+ * aic_step_attention_win(...) == aic_step_attention_dt(..., sliding_window, sinks, AIC_DT_BF16, stream). */
+int aic_step_attention_dt(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache, int64_t block_stride,
+                          int kv_dtype, const float* k_scale, const float* v_scale, const int32_t* block_table,
+                          int max_blocks_per_seq, const int32_t* seq_lens, const int32_t* query_start_loc, int batch,
+                          int num_tokens, int num_q_heads, int num_kv_heads, int head_size, int block_size,
+                          float sm_scale, void* out, int64_t out_stride, void* workspace, size_t workspace_bytes,
+                          int max_seq_len, const int32_t* req_lists, int n_short, int n_prefill, int n_long,
+                          const int32_t* decode_query_start_loc, const int32_t* decode_token_index,
+                          int num_decode_tokens, int max_decode_q_len, int max_prefill_q_len, int sliding_window,
+                          const float* sinks, int q_dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A12  Ulysses head/sequence repartition — the copies around the two all-to-alls of

@@ -61,6 +61,51 @@ def attn(B=64, ctx=4096, qlen=4, Hq=32, Hkv=8, D=128, bs=16, layers=4, split=Fal
     print(f"attn{' fp8kv' if kv8 else ''} B={B} ctx={ctx} qlen={qlen} Hq={Hq} Hkv={Hkv} D={D}: {us:8.1f} us  {gb / us * 1e6 / 1e3:6.2f} TB/s (incl. combine)")
 
 
+def attn_dtypes(B=64, ctx=4096, qlen=4, Hq=32, Hkv=8, D=128, bs=16, layers=4, split=False, kv8=False, n_short=0, n_long=0,
+                rounds=5, iters=20):
+    """attn() / attn_mix() geometry for a bf16 and an fp16 model in ONE process, alternating: same block table, same
+    request lists, fresh random q / caches of each type (an e4m3 cache is shared).  `rounds` timed windows per type,
+    interleaved bf16, fp16, bf16, ...; prints each type's minimum, median and maximum and the ratio of the medians, so the
+    difference between the types can be read against the run's own spread."""
+    ql = [1] * n_short + [33] * n_long if (n_short or n_long) else [qlen] * B
+    B = len(ql)
+    nblk = (ctx + bs - 1) // bs
+    nb = B * nblk
+    bt = torch.randperm(nb, device=dev).to(torch.int32).view(B, nblk)
+    seq = torch.full((B,), ctx, dtype=torch.int32, device=dev)
+    qsl = torch.tensor(np.concatenate([[0], np.cumsum(ql)]).astype(np.int32), device=dev)
+    rs = ops.split_requests(ql, Hq // Hkv, dev) if (split or n_long) else None
+    kw, kv_shared = {}, None
+    if kv8:
+        kv_shared = []
+        for _ in range(layers):
+            raw = torch.randint(0, 256, (2, nb, bs, Hkv, D), dtype=torch.uint8, device=dev)
+            raw[(raw & 0x7f) == 0x7f] = 0x30
+            kv_shared.append(raw.view(torch.float8_e4m3fn))
+        sc = torch.full((1,), 0.02, dtype=torch.float32, device=dev)
+        kw = dict(k_scale=sc, v_scale=sc)
+    fns = {}
+    for name, dt in (("bf16", torch.bfloat16), ("fp16", torch.float16)):
+        kvs = kv_shared or [torch.randn(2, nb, bs, Hkv, D, device=dev, dtype=dt) for _ in range(layers)]
+        q = torch.randn(sum(ql), Hq, D, device=dev, dtype=dt)
+        out = torch.empty_like(q)
+
+        def f(kvs=kvs, q=q, out=out, i=[0]):
+            kv = kvs[i[0] % layers]
+            i[0] += 1
+            ops.verify_attention(q, kv[0], kv[1], bt, seq, qsl, max(ql), ctx, D ** -0.5, out=out, req_split=rs, **kw)
+        fns[name] = f
+    times = {name: [] for name in fns}
+    for _ in range(rounds):
+        for name, f in fns.items():
+            times[name].append(timeit(f, iters=iters))
+    med = {name: float(np.median(t)) for name, t in times.items()}
+    shape = f"short={n_short}x1 long={n_long}x33" if (n_short or n_long) else f"B={B} qlen={qlen}"
+    print(f"attn-dtypes{' fp8kv' if kv8 else ''} {shape} ctx={ctx} Hq={Hq} Hkv={Hkv} D={D}{' lists' if rs else ''}: " +
+          "  ".join(f"{name} min {min(t):7.1f} med {med[name]:7.1f} max {max(t):7.1f} us" for name, t in times.items()) +
+          f"  fp16 / bf16 {med['fp16'] / med['bf16']:.3f}", flush=True)
+
+
 def attn_mix(n_short=59, n_long=5, q_short=1, q_long=33, ctx=4224, Hq=32, Hkv=8, D=128, bs=16, layers=4, kv8=False):
     """The steady-state step of bench.py: most requests carry no draft (q_len 1), a few a long suffix draft — one call
     through the host-partitioned path (pair kernel) against its parts."""
@@ -530,6 +575,22 @@ if __name__ == "__main__":
     if "fp8" in what or "attn" in what:
         attn(split=True, kv8=True)
         attn(B=16, qlen=33, split=True, kv8=True)
+    if "attn16" in what:     # attn's shapes for a bf16 and an fp16 model, alternating in this process (a mode of its own:
+        #                      `attn` is a stage of collect_profiles.sh and keeps its length)
+        attn_dtypes(split=True)
+        attn_dtypes()
+        attn_dtypes(B=32)
+        attn_dtypes(B=8)
+        attn_dtypes(B=64, Hq=4, Hkv=1)
+        attn_dtypes(B=64, qlen=8)
+        attn_dtypes(B=16, qlen=33, split=True)
+        attn_dtypes(B=4, qlen=33, split=True)
+        attn_dtypes(B=1, qlen=33, split=True)
+        attn_dtypes(B=64, Hq=64, Hkv=8, D=64)
+        attn_dtypes(B=64, Hq=8, Hkv=1, D=64)
+        attn_dtypes(split=True, kv8=True)
+        attn_dtypes(B=16, qlen=33, split=True, kv8=True)
+        attn_dtypes(n_short=59, n_long=5, ctx=4224)          # attn_mix's step: the one-grid short + long launch
     if "long" in what:
         attn(B=16, qlen=33, split=True)
         attn(B=16, qlen=17, split=True)
