@@ -439,25 +439,31 @@ __device__ __forceinline__ void verify_attn_body(const AttnParams& P, uint4* v_l
   }
 
   // Software pipeline with ONE register set per operand: the registers of a tile are re-armed with the
-  // next tile's loads as soon as their last consumer has issued (V: right after its LDS write, K: right
-  // after the QK^T MFMAs), so each load has about a full iteration to land and the kernel stays under
-  // 168 VGPRs (3 waves per SIMD = 12 x 16 KiB in flight per CU).  Loads past a wave's range are clamped
-  // into the context by tile_pages(): always valid addresses, results never used.
+  // next tile's loads once their last consumer has issued (V: its LDS write, K: the QK^T MFMAs), so each
+  // load has about a full iteration to land and the kernel stays under 168 VGPRs (3 waves per SIMD =
+  // 12 x 16 KiB in flight per CU).  Nothing is requested past the wave's range: the tile behind it is
+  // another wave's, and loading it here read it from HBM a second time (16 KiB per wave, in the last
+  // microseconds of the launch).  Both operands are re-armed in ONE wave-uniform branch placed after the
+  // QK^T MFMAs, where the compiler's schedule had put all 16 loads anyway: no load is in flight at the
+  // branch, so the vmcnt waits of the steady state are those of the unconditional form.  (A branch around
+  // the V loads alone, ahead of the MFMAs, makes the wait for K(t) drain V(t+1) as well; the last tile as a
+  // compile-time copy of the body costs a wave with a short range more in instruction fetch than the
+  // loads it saves: +1 us on the 18 us call of an SP = 8 rank slice at 1056 tokens)
   if (t_begin < t_end) {
     TilePages pages = tile_pages(t_begin);
     AIC_LOAD_V(t_begin, pages)
     AIC_LOAD_K(t_begin, pages)
-    TilePages pages_next = tile_pages(t_begin + kTile);
+    TilePages pages_next = pages;
+    if (t_begin + kTile < t_end) pages_next = tile_pages(t_begin + kTile);
     AIC_PSTAMP(2)
 
     for (int tt = t_begin; tt < t_end; tt += kTile) {
       const int tn = tt + kTile;
-      // 1. V(t) registers -> wave-private LDS tile; 2. re-arm them with V(t+1)
+      // 1. V(t) registers -> wave-private LDS tile
       AIC_STORE_V(0, v0) AIC_STORE_V(1, v1) AIC_STORE_V(2, v2) AIC_STORE_V(3, v3)
       AIC_STORE_V(4, v4) AIC_STORE_V(5, v5) AIC_STORE_V(6, v6) AIC_STORE_V(7, v7)
-      AIC_LOAD_V(tn, pages_next)
 
-      // 3. S^T tiles (K registers), online softmax per 16-row query tile
+      // 2. S^T tiles (K registers), online softmax per 16-row query tile
       // P is split into a bf16 head and a bf16 tail (p = hi + lo up to 2^-17 relative): the kernel is
       // HBM-bound with the matrix pipe a few percent busy, so a second P.V MFMA is free and removes the
       // 2^-9 relative rounding a single bf16 P would put on every term
@@ -484,9 +490,12 @@ __device__ __forceinline__ void verify_attn_body(const AttnParams& P, uint4* v_l
         st[mt][0] = a0;
         st[mt][1] = a1;
       }
-      // 4. re-arm the K registers with K(t+1); page lookup one tile ahead of its data loads
-      AIC_LOAD_K(tn, pages_next)
-      pages_next = tile_pages(tn + kTile);
+      // 3. re-arm the V and K registers with tile t+1 if the range has one; page lookup one tile ahead of its data loads
+      if (tn < t_end) {
+        AIC_LOAD_V(tn, pages_next)
+        AIC_LOAD_K(tn, pages_next)
+        if (tn + kTile < t_end) pages_next = tile_pages(tn + kTile);
+      }
 
       V8 pfrag[MTQ], pfrag_lo[MTQ];
       // the tile reaches the causal edge / range end, or (window) lies below the last row's lower bound ctx - window
@@ -497,7 +506,7 @@ __device__ __forceinline__ void verify_attn_body(const AttnParams& P, uint4* v_l
                          inv_scale, m_run[mt], l_run[mt], o_acc[mt], pfrag[mt], pfrag_lo[mt]);
       }
 
-      // 5. O^T += V^T P^T : A = V^T fragment via transposing LDS reads
+      // 4. O^T += V^T P^T : A = V^T fragment via transposing LDS reads
       {
         const int q4 = c16 >> 2, p4 = c16 & 3;
 #pragma unroll
