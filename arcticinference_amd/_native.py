@@ -113,6 +113,7 @@ _SIGNATURES = {
     "aic_debug_attn_light": (c_int, [c_int]),
     "aic_debug_attn_graph": (c_int, [c_int]),
     "aic_debug_attn_long_splits": (c_int, [c_int]),
+    "aic_debug_attn_prefix_splits": (c_int, [c_int]),
     "aic_debug_attn_long_dma": (c_int, [c_int]),
     "aic_debug_attn_graph_stats": (c_int, [POINTER(c_uint64), POINTER(c_uint64)]),
     "aic_row_gather": (c_int, [c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_int64), POINTER(c_int64),
@@ -164,6 +165,10 @@ _SIGNATURES = {
                                         c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                         c_int, c_float, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_void_p, c_int,
                                         c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "aic_verify_attention_prefix": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
+                                            c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                            c_int, c_float, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_void_p, c_int,
+                                            c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "aic_step_attention_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "aic_step_attention": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                    c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,

@@ -34,17 +34,15 @@
 
 #include "aic_common.h"
 #include "attn_common.h"
+#include "pf_tile.h"
 
 namespace aic {
 namespace {
 
-constexpr int kPfWaves = 4;
-constexpr int kPfMT = 2;                        // 16-row MFMA tiles per wave
-constexpr int kPfRows = kPfWaves * kPfMT * 16;  // query rows (token x head of the group) per workgroup
+// (workgroup shape — kPfWaves, kPfMT, kPfRows — and the tile step itself: pf_tile.h, shared with prefix_attn.hip)
 constexpr int kPfTargetWgs = 256;               // below this many workgroups a call splits its key ranges (MI355X: 256 CUs)
 constexpr int kPfMaxSplits = 16;
 constexpr int kPfMinSplitTiles = 8;             // at least 256 keys per split
-constexpr float kPfSlack = 6.0f;                // lazy maximum: a row's adopted maximum may trail the true one by 2^6
 
 struct PrefillParams {
   const uint16_t* q;
@@ -98,13 +96,11 @@ __device__ __forceinline__ PfItem pf_item(const PrefillParams& P, int wgi) {
 template <int D, bool KV8, bool WIN, typename E = ElemBf16>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) prefill_attn_kernel(PrefillParams P) {
   static_assert(D == 128 || (D == 64 && !KV8), "head size 128, or 64 with a 16-bit cache");
-  using V8 = typename E::vec8;
-  constexpr int DT = D / 16;   // 16-wide output tiles
-  constexpr int NS = D / 32;   // k-steps of mfma_f32_16x16x32_bf16 per S tile
-  constexpr int ES = KV8 ? 1 : 2;
-  constexpr bool ONE_CHUNK = KV8 || D == 64;  // a token row of one head is 128 bytes: one 16-byte chunk of K and of V per thread
+  using T = PfTile<D, KV8, E>;
+  constexpr int DT = T::DT, NS = T::NS, ES = T::ES;
+  constexpr bool ONE_CHUNK = T::ONE_CHUNK;
   // [buffer][K, V] 32-token tiles in the verify bodies' image (tile_off<D>): read row-wise for K, transposed for V
-  __shared__ uint4 lds[2][2][kTile * D / 8];
+  __shared__ uint4 lds[2][2][T::kTileU4];
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -173,7 +169,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
   const_i32_ptr btab = (const_i32_ptr)(P.block_table + static_cast<int64_t>(req) * P.max_blocks);
   const int last_group = (ctx - 1) & ~15;
   const int tid = threadIdx.x;
-  uint4 kr0, kr1, vr0, vr1;
+  typename T::Regs r;
   auto group_base = [&](int first) -> int64_t {   // element offset of token `first` of kv head h
     const unsigned f = static_cast<unsigned>(first), bs = static_cast<unsigned>(P.block_size);
     const unsigned pg = P.bs_shift >= 0 ? f >> P.bs_shift : f / bs;
@@ -189,18 +185,18 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
       const int64_t base = ti < 16 ? b0 : b1;
       const unsigned off = static_cast<unsigned>(min(tt + ti, ctx - 1) - first);
       const size_t byte = static_cast<size_t>(base) * ES + __umul24(off, row_bytes) + 16u * ch;
-      kr0 = ld_kv16(P.k_cache + byte);
-      vr0 = ld_kv16(P.v_cache + byte);
+      r.k0 = ld_kv16(P.k_cache + byte);
+      r.v0 = ld_kv16(P.v_cache + byte);
     } else {
       const int ti = tid >> 4, ch = tid & 15;
       const unsigned off0 = static_cast<unsigned>(min(tt + ti, ctx - 1) - f0);
       const unsigned off1 = static_cast<unsigned>(min(tt + 16 + ti, ctx - 1) - f1);
       const size_t y0 = static_cast<size_t>(b0) * 2 + __umul24(off0, row_bytes) + 16u * ch;
       const size_t y1 = static_cast<size_t>(b1) * 2 + __umul24(off1, row_bytes) + 16u * ch;
-      kr0 = ld_kv16(P.k_cache + y0);
-      kr1 = ld_kv16(P.k_cache + y1);
-      vr0 = ld_kv16(P.v_cache + y0);
-      vr1 = ld_kv16(P.v_cache + y1);
+      r.k0 = ld_kv16(P.k_cache + y0);
+      r.k1 = ld_kv16(P.k_cache + y1);
+      r.v0 = ld_kv16(P.v_cache + y0);
+      r.v1 = ld_kv16(P.v_cache + y1);
     }
   };
   // V of keys below every row's window (the first tile of a windowed range) is staged as zeros: their weights are 0,
@@ -211,107 +207,29 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
     if (WIN && tt < key_lo) {
       const uint4 z = make_uint4(0, 0, 0, 0);
       if (ONE_CHUNK) {
-        if (tt + (tid >> 3) < key_lo) vr0 = z;
+        if (tt + (tid >> 3) < key_lo) r.v0 = z;
       } else {
-        if (tt + (tid >> 4) < key_lo) vr0 = z;
-        if (tt + 16 + (tid >> 4) < key_lo) vr1 = z;
+        if (tt + (tid >> 4) < key_lo) r.v0 = z;
+        if (tt + 16 + (tid >> 4) < key_lo) r.v1 = z;
       }
     }
-    if (KV8) {
-      const int ti = tid >> 3, ch = 2 * (tid & 7);
-      *reinterpret_cast<V8*>(kt + v_tile_off(ti, ch)) = E::from_fp8(kr0.x, kr0.y);
-      *reinterpret_cast<V8*>(kt + v_tile_off(ti, ch + 1)) = E::from_fp8(kr0.z, kr0.w);
-      *reinterpret_cast<V8*>(vt + v_tile_off(ti, ch)) = E::from_fp8(vr0.x, vr0.y);
-      *reinterpret_cast<V8*>(vt + v_tile_off(ti, ch + 1)) = E::from_fp8(vr0.z, vr0.w);
-    } else if (D == 64) {
-      const int ti = tid >> 3, ch = tid & 7;
-      *reinterpret_cast<uint4*>(kt + tile_off<64>(ti, ch)) = kr0;
-      *reinterpret_cast<uint4*>(vt + tile_off<64>(ti, ch)) = vr0;
-    } else {
-      const int ti = tid >> 4, ch = tid & 15;
-      *reinterpret_cast<uint4*>(kt + v_tile_off(ti, ch)) = kr0;
-      *reinterpret_cast<uint4*>(kt + v_tile_off(16 + ti, ch)) = kr1;
-      *reinterpret_cast<uint4*>(vt + v_tile_off(ti, ch)) = vr0;
-      *reinterpret_cast<uint4*>(vt + v_tile_off(16 + ti, ch)) = vr1;
-    }
+    T::store(kt, vt, tid, r);
   };
 
   // one 32-token tile against the wave's 32 rows (wave-uniform call: the transposed reads need every lane)
   auto compute_tile = [&](int buf, int tt) {
-    const char* kt = reinterpret_cast<const char*>(lds[buf][0]);
-    const char* vt = reinterpret_cast<const char*>(lds[buf][1]);
-    V8 kf[2][NS];  // A operand: key 16 th + c16, d = 32 s + 8 g + j
-#pragma unroll
-    for (int th = 0; th < 2; ++th)
-#pragma unroll
-      for (int s = 0; s < NS; ++s) kf[th][s] = *reinterpret_cast<const V8*>(kt + tile_off<D>(16 * th + c16, 4 * s + g));
     // the tile crosses the causal edge of a row of the wave, or (window) holds a key at or below a row's lim - window
     const bool need_mask = tt + kTile - 1 > w_lim_lo || (WIN && tt <= w_lim_hi - wnd);
-    V8 pf[kPfMT], pl[kPfMT];  // P = head + tail (E each): one bf16 P would put 2^-9 on every weight
+    T::compute(reinterpret_cast<const char*>(lds[buf][0]), reinterpret_cast<const char*>(lds[buf][1]), g, c16, qf, m_run, l_run,
+               o_acc, scale_log2, inv_scale, [&](int mt, float (&sc)[8]) {
+                 if (need_mask) {
 #pragma unroll
-    for (int mt = 0; mt < kPfMT; ++mt) {
-      f32x4 a0 = f32x4{0.f, 0.f, 0.f, 0.f}, a1 = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int s = 0; s < NS; ++s) {
-        a0 = E::mfma(kf[0][s], __builtin_bit_cast(V8, qf[mt][s]), a0);
-        a1 = E::mfma(kf[1][s], __builtin_bit_cast(V8, qf[mt][s]), a1);
-      }
-      // lane (c16, g) holds row c16's scores of keys tt + 4 g + e (a0) and tt + 16 + 4 g + e (a1)
-      float sc[8];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        sc[e] = a0[e];
-        sc[4 + e] = a1[e];
-      }
-      if (need_mask) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const int key = tt + 16 * (e >> 2) + 4 * g + (e & 3);
-          if (key > lim[mt] || (WIN && key <= lim[mt] - wnd)) sc[e] = -INFINITY;
-        }
-      }
-      float lmax = sc[0];
-#pragma unroll
-      for (int e = 1; e < 8; ++e) lmax = fmaxf(lmax, sc[e]);
-      // raw score above which the row adopts a new maximum (-inf while nothing is visible: any finite score does)
-      const float thr = __builtin_fmaf(m_run[mt], inv_scale, kPfSlack * inv_scale);
-      if (__any(lmax > thr)) {
-        const float m_new = fmaxf(m_run[mt], rowgroup_max(lmax) * scale_log2);
-        const float m_to = m_new == -INFINITY ? 0.0f : m_new;
-        const float alpha = __builtin_amdgcn_exp2f(m_run[mt] - m_to);
-        m_run[mt] = m_new;
-        l_run[mt] *= alpha;
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) o_acc[mt][dt] *= alpha;
-      }
-      const float m_use = m_run[mt] == -INFINITY ? 0.0f : m_run[mt];
-      float ls = 0.0f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[e], scale_log2, -m_use));
-        pf[mt][e] = E::head(p);
-        pl[mt][e] = E::tail(p, pf[mt][e]);
-        ls += p;
-      }
-      l_run[mt] += ls;
-    }
-    // O^T += V^T P^T: lane 4q+p of a 16-lane group supplies row q of the 4-token block, columns 4p..4p+3
-    const int q4 = c16 >> 2, p4 = c16 & 3;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) {
-      const char* a_lo = vt + tile_off<D>(4 * g + q4, 2 * dt + (p4 >> 1)) + 8 * (p4 & 1);
-      const char* a_hi = vt + tile_off<D>(16 + 4 * g + q4, 2 * dt + (p4 >> 1)) + 8 * (p4 & 1);
-      const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(const_cast<char*>(a_lo)));
-      const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(const_cast<char*>(a_hi)));
-      typedef __attribute__((ext_vector_type(8))) short s16x8;
-      const V8 vfrag = __builtin_bit_cast(V8, static_cast<s16x8>(__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7)));
-#pragma unroll
-      for (int mt = 0; mt < kPfMT; ++mt)
-      {
-        o_acc[mt][dt] = E::mfma(vfrag, pf[mt], o_acc[mt][dt]);
-        o_acc[mt][dt] = E::mfma(vfrag, pl[mt], o_acc[mt][dt]);
-      }
-    }
+                   for (int e = 0; e < 8; ++e) {
+                     const int key = tt + 16 * (e >> 2) + 4 * g + (e & 3);
+                     if (key > lim[mt] || (WIN && key <= lim[mt] - wnd)) sc[e] = -INFINITY;
+                   }
+                 }
+               });
   };
 
   if (t_first < t_last) {

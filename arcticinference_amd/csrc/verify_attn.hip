@@ -37,6 +37,7 @@
 
 #include "aic_common.h"
 #include "attn_common.h"
+#include "prefix_attn.h"
 
 namespace aic {
 
@@ -88,6 +89,14 @@ struct AttnParams {
   // at the tile that holds key (ctx - q_len) - window + 1 instead of at 0, and the lower bound joins the causal mask.
   // sinks (f32 [Hq], may be null): one extra logit per head in the soft-max normalisation, no value — it is the initial
   // (max, sum = 1) state of the FIRST partial of every row, so it is counted once however the range is split.
+  // window < 0 (aic_verify_attention_prefix; never together with a real window): the call has a shared prefix of -window
+  // keys, a multiple of the tile, which another launch serves (prefix_attn.hip): a request's token range starts there, with
+  // no lower mask edge.  Only the PFX instantiations of the bodies read it that way, and only such a call launches them.
+  // (Both cheaper forms were built first and cost the DEFAULT call: a scalar of its own up to 26 more spilled SGPRs in the
+  // one-grid kernels, this field read by the shared bodies -22 ... +7, and bench.py's headline then sat 0.16 % under the
+  // parent's, just outside the parent's own spread: profiles/shared_prefix_default_path_ab.txt.)  The slot base of such a
+  // call needs no field: its launches get ws_o / ws_ml advanced past the prefix slots and n_parts_total counted from
+  // there, so slot 0 of THIS launch is still where the sinks start.
   int window;
   const float* sinks;
   // debug (aic_debug_attn_phase_trace): per short-body workgroup (by * ptrace_stride + bx) eight 100 MHz timestamps —
@@ -96,9 +105,12 @@ struct AttnParams {
   int ptrace_stride;
 };
 
-// first token of the range a request's rows can see, rounded down to a tile (0 without a window)
+// first token of the range a request's rows can see, rounded down to a tile: 0 without a window — or, in the PFX copies of
+// the bodies (a call with a shared prefix), the prefix length (clamped to the context, so that a request that breaks the call's precondition and is shorter
+// than the prefix gets an empty range, not a negative one)
+template <bool PFX = false>
 __device__ __forceinline__ int window_begin(const AttnParams& P, int ctx, int q_len) {
-  if (P.window <= 0) return 0;
+  if (P.window <= 0) return PFX ? min(-P.window, ctx) : 0;
   const int lo = ctx - q_len - P.window + 1;
   return lo > 0 ? (lo & ~(kTile - 1)) : 0;
 }
@@ -221,7 +233,7 @@ struct ShortLds {
 // one: K and V are fetched with the fp8 form's lane mapping (two 16-byte K loads per token group, four V loads per tile),
 // used as they are (no conversion), with two k-steps per score MFMA chain and four 16-wide output tiles.
 // E = the call's 16-bit element type (attn_common.h: ElemBf16 | ElemF16): what "bf16" stands for above in an f16 call.
-template <int MTQ, int HPW, bool KV8, int NW, int HD = kD, typename E = ElemBf16>
+template <int MTQ, int HPW, bool KV8, int NW, int HD = kD, typename E = ElemBf16, bool PFX = false>
 __device__ __forceinline__ void verify_attn_body(const AttnParams& P, uint4* v_lds_raw, const int bx, const int by) {
   static_assert(HD == 128 || (HD == 64 && !KV8), "head size 128, or 64 with a 16-bit cache");
   using V8 = typename E::vec8;
@@ -274,7 +286,7 @@ __device__ __forceinline__ void verify_attn_body(const AttnParams& P, uint4* v_l
 
   const int n_parts = P.n_splits * R;
   const int part = by * R + range;
-  const int t_lo = window_begin(P, ctx, q_len);           // 0 unless the layer has a sliding window
+  const int t_lo = window_begin<PFX>(P, ctx, q_len);   // 0 unless the layer has a sliding window or the call a shared prefix
   const int wnd = P.window > 0 ? P.window : (1 << 30);
   const int tiles_total = (ctx - t_lo + kTile - 1) / kTile;
   int t_begin, t_end;
@@ -675,26 +687,29 @@ __device__ __forceinline__ void verify_attn_body(const AttnParams& P, uint4* v_l
 // or a k = 3 draft (<= 16 rows with Hq/Hkv <= 4); suffix drafts of 4-7 tokens (17-32 rows; 46 % of all suffix drafts in
 // the r02 bench, `bench.py --qlen-hist`) used to go through the shared-tile long-draft body, where a request costs ~6 us
 // per layer whatever its length, against ~2.7 us for a workgroup of this streaming body.
-template <int HPW, bool KV8, int NW, int HD = kD, typename E = ElemBf16>
+template <int HPW, bool KV8, int NW, int HD = kD, typename E = ElemBf16, bool PFX = false>
 __device__ __forceinline__ void verify_attn_body_dual(const AttnParams& P, uint4* v_lds_raw, const int bx, const int by) {
   if (bx >= P.n_items) return;             // m_groups == 1: item == bx
   const int ridx = bx / (P.num_kv_heads / HPW);
   const int req = __builtin_amdgcn_readfirstlane(P.req_list ? P.req_list[ridx] : ridx);
   const int q_len = __builtin_amdgcn_readfirstlane(P.query_start_loc[req + 1] - P.query_start_loc[req]);
   if (q_len * (P.num_q_heads / P.num_kv_heads) <= 16)
-    verify_attn_body<1, HPW, KV8, NW, HD, E>(P, v_lds_raw, bx, by);
+    verify_attn_body<1, HPW, KV8, NW, HD, E, PFX>(P, v_lds_raw, bx, by);
   else
-    verify_attn_body<2, HPW, KV8, NW, HD, E>(P, v_lds_raw, bx, by);
+    verify_attn_body<2, HPW, KV8, NW, HD, E, PFX>(P, v_lds_raw, bx, by);
 }
 
 // MTQ = 0: the per-workgroup choice above
-template <int MTQ, int HPW, bool KV8, int NW = 4, int HD = kD, typename E = ElemBf16>
+// PFX: the copy a call with a shared prefix launches (aic_verify_attention_prefix): its token ranges start at the prefix
+// length carried in AttnParams.window (negative).  The default instantiations (PFX = false) know nothing of it and are, to
+// the instruction, what they were before shared prefixes existed.
+template <int MTQ, int HPW, bool KV8, int NW = 4, int HD = kD, typename E = ElemBf16, bool PFX = false>
 __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((MTQ == 1 && NW == 4) ? 3 : 2, (MTQ == 1 && NW == 4) ? 3 : 2))) verify_attn_kernel(AttnParams P) {
   __shared__ uint4 v_lds_raw[ShortLds<MTQ == 0 ? 2 : MTQ, NW, HD>::kU4];
   if constexpr (MTQ == 0)
-    verify_attn_body_dual<HPW, KV8, NW, HD, E>(P, v_lds_raw, blockIdx.x, blockIdx.y);
+    verify_attn_body_dual<HPW, KV8, NW, HD, E, PFX>(P, v_lds_raw, blockIdx.x, blockIdx.y);
   else
-    verify_attn_body<MTQ, HPW, KV8, NW, HD, E>(P, v_lds_raw, blockIdx.x, blockIdx.y);
+    verify_attn_body<MTQ, HPW, KV8, NW, HD, E, PFX>(P, v_lds_raw, blockIdx.x, blockIdx.y);
 }
 
 // One 32-token KV tile (K and V images in LDS at kb / vb, v_tile_off layout) against the NT row tiles of a wave
@@ -915,7 +930,7 @@ constexpr int kLong4LdsU4 = kLongRing * 2 * kTile * 16;
 // D = 64 (bf16 cache only): 128-byte rows, i.e. the DMA geometry of the fp8 case without the conversion (long drafts of a
 // head-size-64 model; requests of up to 32 rows take the streaming body's HD = 64 form).
 // E = the call's 16-bit element type (ElemBf16 | ElemF16): the images' type, "bf16" above, in an f16 call.
-template <bool KV8, int D, bool TR = false, typename E = ElemBf16>
+template <bool KV8, int D, bool TR = false, typename E = ElemBf16, bool PFX = false>
 __device__ __forceinline__ void verify_attn_long4_body(const AttnParams& P, uint4* lds, const int bx, const int by, const int bz) {
   static_assert(D == 128 || (D == 64 && !KV8), "head size 128, or 64 with a 16-bit cache");
   uint64_t cyc[6] = {0, 0, 0, 0, 0, 0};   // TR: [0] issuing the next tile's DMA, [1..3] long_tile_compute, [4] vmcnt wait, [5] barrier
@@ -946,7 +961,7 @@ __device__ __forceinline__ void verify_attn_long4_body(const AttnParams& P, uint
   const int row_base = bz * (4 * RT * 16);
   if (row_base >= n_rows) return;
 
-  const int t_lo = window_begin(P, ctx, q_len);
+  const int t_lo = window_begin<PFX>(P, ctx, q_len);
   const int wnd = P.window > 0 ? P.window : (1 << 30);
   const int tiles_total = (ctx - t_lo + kTile - 1) / kTile;
   const int tiles_per_part = (tiles_total + P.n_splits - 1) / P.n_splits;
@@ -1379,10 +1394,10 @@ __device__ __forceinline__ void verify_attn_long4_body(const AttnParams& P, uint
   }
 }
 
-template <bool KV8, int D = 128, bool TR = false, typename E = ElemBf16>
+template <bool KV8, int D = 128, bool TR = false, typename E = ElemBf16, bool PFX = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) verify_attn_long4_kernel(AttnParams P) {
   __shared__ __attribute__((aligned(1024))) uint4 lds[kLong4LdsU4];
-  verify_attn_long4_body<KV8, D, TR, E>(P, lds, blockIdx.x, blockIdx.y, blockIdx.z);
+  verify_attn_long4_body<KV8, D, TR, E, PFX>(P, lds, blockIdx.x, blockIdx.y, blockIdx.z);
 }
 
 // Short requests and long drafts of one call in ONE launch: workgroups [0, n_long_wg) run the long-draft body,
@@ -1751,11 +1766,16 @@ static int verify_attention_impl(const void* q, int64_t q_stride, const void* k_
                                  int num_kv_heads, int head_size, int block_size, float sm_scale, void* out,
                                  int64_t out_stride, void* workspace, size_t workspace_bytes, int max_seq_len_full,
                                  const int32_t* short_reqs, int n_short, const int32_t* long_reqs, int n_long,
-                                 int sliding_window, const float* sinks, void* stream) {
+                                 int sliding_window, const float* sinks, void* stream, int prefix_len = 0,
+                                 const int32_t* prefix_table = nullptr) {
+  // prefix_len > 0 (a multiple of the tile; aic_verify_attention_prefix): keys [0, prefix_len) of every request are the
+  // pages of prefix_table and go through the prefix body, the bodies launched here start at prefix_len
   constexpr bool kTraceable = std::is_same<E, ElemBf16>::value;
   AIC_REQUIRE(sliding_window >= 0, "sliding_window must be >= 0 (0 = none)");
   // what a request streams at most: the whole context, or — sliding window — the window plus the draft and tile slack
-  const int max_seq_len = sliding_window > 0 ? std::min(max_seq_len_full, sliding_window + max_q_len + kTile) : max_seq_len_full;
+  // — or, with a shared prefix, what lies behind it
+  const int max_seq_len = sliding_window > 0 ? std::min(max_seq_len_full, sliding_window + max_q_len + kTile)
+                                             : max_seq_len_full - prefix_len;
   AIC_REQUIRE(q && k_cache && v_cache && block_table && seq_lens && query_start_loc && out && workspace,
               "null pointer argument to aic_verify_attention");
   AIC_REQUIRE(batch > 0 && num_tokens > 0 && max_q_len > 0 && num_q_heads > 0 && num_kv_heads > 0 && block_size > 0 &&
@@ -1803,7 +1823,7 @@ static int verify_attention_impl(const void* q, int64_t q_stride, const void* k_
     n_splits = pick_splits(batch * hgroups, max_seq_len, wave_heads ? 2 : 8, 1, 0);
   }
   const int hgroups_s = num_kv_heads / hpw;              // head groups of the short launch
-  const bool direct = split_lists && n_short > 0 && n_splits == 1;
+  const bool direct = split_lists && n_short > 0 && n_splits == 1 && prefix_len == 0;   // a prefix: every row needs the merge
   int n_splits_long = (split_lists && n_long > 0) ? pick_splits(n_long * num_kv_heads, max_seq_len, mixed ? 4 : 8, 2) : 0;
   // The long part of a mixed call: its workgroups start first and should end with the short ones.  Per-workgroup traces
   // (tools/microbench.py sptrace / longsplits, 4224-token contexts, profiles/r02_long_splits.txt): a short workgroup takes
@@ -1835,16 +1855,33 @@ static int verify_attention_impl(const void* q, int64_t q_stride, const void* k_
     const int per_split_ = n_long * num_kv_heads * long_z_;
     const int fit = (2 * cu_count() - short_wg_) / per_split_;
     const bool want = g_force_sequential >= 0 ? g_force_sequential == 1 : (fit == 1 && n_splits_long >= 2);
-    if (fit < 1 || want) {
+    // (a call with a shared prefix always: the one-grid kernel has no prefix-carrying copy — it is the project's largest
+    // and slowest to compile, and the bodies it is made of exist as such copies on their own)
+    if (fit < 1 || want || prefix_len > 0) {
       sequential = true;
       n_splits_long = pick_splits(n_long * num_kv_heads, max_seq_len, 8, 2);
     }
   }
   auto fits = [&](int parts) { return static_cast<size_t>(parts) * rows * (head_size + 2) * sizeof(float) <= workspace_bytes; };
-  while (n_splits > 1 && !fits(n_splits)) --n_splits;
-  while (n_splits_long > 1 && !fits(n_splits_long)) --n_splits_long;
-  AIC_REQUIRE(fits(n_splits), "workspace too small (%zu bytes)", workspace_bytes);
-  const int n_parts_total = std::max(n_splits, n_splits_long);
+  // Slots of a row: the prefix launch's first (n_pre of them, none without a prefix), then this call's own.  That order
+  // keeps the combine kernel's conventions: a sentinel (l = -2) behind a row's last suffix slot hides nothing that is
+  // live, and slot 0 never holds l = -1 (a prefix partial's sum is positive; direct output is off).  At most 64 in all,
+  // at least one of each kind, and the suffix launches give way to the workspace before the prefix launch does.
+  int n_pre = 0;
+  if (prefix_len > 0) {
+    while (std::max(n_splits, n_splits_long) > 63) {
+      if (n_splits > 63) --n_splits;
+      if (n_splits_long > 63) --n_splits_long;
+    }
+    n_pre = prefix_pick_splits(num_tokens, num_q_heads, num_kv_heads, prefix_len, 64 - std::max(n_splits, n_splits_long),
+                               cu_count());
+    while (n_pre > 1 && !fits(n_pre + std::max(n_splits, n_splits_long))) --n_pre;
+  }
+  while (n_splits > 1 && !fits(n_pre + n_splits)) --n_splits;
+  while (n_splits_long > 1 && !fits(n_pre + n_splits_long)) --n_splits_long;
+  AIC_REQUIRE(fits(n_pre + n_splits), "workspace too small (%zu bytes)", workspace_bytes);
+  const int n_parts_own = std::max(n_splits, n_splits_long);   // slots of the launches below, counted from slot n_pre
+  const int n_parts_total = n_pre + n_parts_own;
 
   AttnParams P;
   P.q = static_cast<const uint16_t*>(q);
@@ -1853,8 +1890,10 @@ static int verify_attention_impl(const void* q, int64_t q_stride, const void* k_
   P.block_table = block_table;
   P.seq_lens = seq_lens;
   P.query_start_loc = query_start_loc;
-  P.ws_o = static_cast<float*>(workspace);
-  P.ws_ml = P.ws_o + static_cast<size_t>(n_parts_total) * rows * head_size;
+  float* const ws_o_all = static_cast<float*>(workspace);
+  float* const ws_ml_all = ws_o_all + static_cast<size_t>(n_parts_total) * rows * head_size;
+  P.ws_o = ws_o_all + static_cast<size_t>(n_pre) * rows * head_size;
+  P.ws_ml = ws_ml_all + static_cast<size_t>(n_pre) * rows * 2;
   P.q_stride = q_stride;
   P.block_stride = block_stride;
   P.max_blocks = max_blocks_per_seq;
@@ -1864,7 +1903,7 @@ static int verify_attention_impl(const void* q, int64_t q_stride, const void* k_
   P.long_dma = g_long_dma;
   P.bs_shift = (block_size & (block_size - 1)) == 0 ? __builtin_ctz(static_cast<unsigned>(block_size)) : -1;
   P.n_splits = n_splits;
-  P.n_parts_total = n_parts_total;
+  P.n_parts_total = n_parts_own;
   P.total_rows = static_cast<int>(rows);
   P.sm_scale = sm_scale;
   P.req_list = nullptr;
@@ -1881,20 +1920,77 @@ static int verify_attention_impl(const void* q, int64_t q_stride, const void* k_
   P.light_first = 0;
   P.light_stride = 0;
   P.light_pct = 100;
-  P.window = sliding_window;
+  P.window = prefix_len > 0 ? -prefix_len : sliding_window;
   P.sinks = sinks;
 
   hipStream_t s = static_cast<hipStream_t>(stream);
   int rc;
+  // The prefix phase runs BESIDE the others, on the library's side stream (fork here, join in front of the combine launch):
+  // its few hundred MFMA-bound workgroups then share the CUs with the HBM-bound suffix launch instead of delaying it.
+  // Measured at 64 requests x 4 tokens, 4224-token contexts, P = 2048, bf16 cache (tools/microbench.py prefix,
+  // profiles/shared_prefix_microbench.txt): ahead on the call's stream 124.3 us per call, beside it 119.0 (fp8 cache:
+  // 86.9 / 75.1; plain call 144 / 83).  The fork and join cost a small call ~10 us (8 requests: 37.9 -> 47.8 us against
+  // 33 plain) — calls the prefix form loses either way.
+  SideStream* pside = nullptr;
+  // whatever ends the call — an error return below included — the call's stream waits for the side stream first: the
+  // prefix launch writes the caller's workspace, and the caller may reuse it as soon as `stream` says the call is over
+  struct PrefixJoin {
+    SideStream*& side;
+    hipStream_t s;
+    bool forked = false, recorded = false, joined = false;
+    ~PrefixJoin() {
+      if (!forked || joined) return;
+      if (!recorded) (void)hipEventRecord(side->join, side->stream);
+      (void)hipStreamWaitEvent(s, side->join, 0);
+    }
+  } prefix_join{pside, s};
+  if (prefix_len > 0) {
+    if ((rc = side_stream(&pside)) != AIC_OK) return rc;
+    AIC_HIP_TRY(hipEventRecord(pside->fork, s));
+    prefix_join.forked = true;
+    AIC_HIP_TRY(hipStreamWaitEvent(pside->stream, pside->fork, 0));
+    PrefixArgs A;
+    A.q = q;
+    A.k_cache = k_cache;
+    A.v_cache = v_cache;
+    A.table = prefix_table;
+    A.k_scale = k_scale;
+    A.v_scale = v_scale;
+    A.ws_o = ws_o_all;
+    A.ws_ml = ws_ml_all;
+    A.q_stride = q_stride;
+    A.block_stride = block_stride;
+    A.num_tokens = num_tokens;
+    A.num_q_heads = num_q_heads;
+    A.num_kv_heads = num_kv_heads;
+    A.head_size = head_size;
+    A.block_size = block_size;
+    A.prefix_len = prefix_len;
+    A.n_splits = n_pre;
+    A.sm_scale = sm_scale;
+    A.kv8 = kv8;
+    A.f16 = std::is_same<E, ElemF16>::value;
+    if ((rc = launch_prefix_attention(A, pside->stream)) != AIC_OK) return rc;
+    // (a head-size-64 call with long drafts records this event again behind its long part, later on the same in-order
+    // stream: the wait below then covers both)
+    AIC_HIP_TRY(hipEventRecord(pside->join, pside->stream));
+    prefix_join.recorded = true;
+  }
   // short / generic kernel for (row tiles, heads per workgroup, cache dtype)
   auto launch_short = [&](int mtq_, int hpw_, dim3 grid_) {
-#define AIC_SHORT(MTQ_, HPW_)                                                                  \
+#define AIC_SHORT_P(MTQ_, HPW_, PFX_)                                                          \
   if (d64)                                                                                     \
-    launch(verify_attn_kernel<MTQ_, HPW_, false, 4, 64, E>, grid_, dim3(256), s, P);           \
+    launch(verify_attn_kernel<MTQ_, HPW_, false, 4, 64, E, PFX_>, grid_, dim3(256), s, P);     \
   else if (kv8)                                                                                \
-    launch(verify_attn_kernel<MTQ_, HPW_, true, 4, kD, E>, grid_, dim3(256), s, P);            \
+    launch(verify_attn_kernel<MTQ_, HPW_, true, 4, kD, E, PFX_>, grid_, dim3(256), s, P);      \
   else                                                                                         \
-    launch(verify_attn_kernel<MTQ_, HPW_, false, 4, kD, E>, grid_, dim3(256), s, P);
+    launch(verify_attn_kernel<MTQ_, HPW_, false, 4, kD, E, PFX_>, grid_, dim3(256), s, P);
+#define AIC_SHORT(MTQ_, HPW_)                                                                  \
+  if (prefix_len > 0) {                                                                        \
+    AIC_SHORT_P(MTQ_, HPW_, true)                                                              \
+  } else {                                                                                     \
+    AIC_SHORT_P(MTQ_, HPW_, false)                                                             \
+  }
     if (mtq_ == 0) {
       if (hpw_ == 4) { AIC_SHORT(0, 4) } else if (hpw_ == 2) { AIC_SHORT(0, 2) } else { AIC_SHORT(0, 1) }
     } else if (mtq_ == 1) {
@@ -1903,6 +1999,7 @@ static int verify_attention_impl(const void* q, int64_t q_stride, const void* k_
       if (hpw_ == 4) { AIC_SHORT(2, 4) } else if (hpw_ == 2) { AIC_SHORT(2, 2) } else { AIC_SHORT(2, 1) }
     }
 #undef AIC_SHORT
+#undef AIC_SHORT_P
   };
   if (!split_lists) {
     if (!t_rec) profile_begin(s);
@@ -2013,7 +2110,7 @@ static int verify_attention_impl(const void* q, int64_t q_stride, const void* k_
       dim3 grid(static_cast<unsigned>(n_long * num_kv_heads), n_splits_long, (max_rows + per_block_rows - 1) / per_block_rows);
       bool traced = false;
       if constexpr (kTraceable) {
-        if (g_attn_ptrace && !d64 && !kv8 && n_short == 0 && static_cast<int>(grid.x * grid.y * grid.z) * 8 <= g_attn_ptrace_cap) {
+        if (g_attn_ptrace && prefix_len == 0 && !d64 && !kv8 && n_short == 0 && static_cast<int>(grid.x * grid.y * grid.z) * 8 <= g_attn_ptrace_cap) {
           PL.ptrace = g_attn_ptrace;   // debug: per-wave cycle accounting of a long-only call (tools/microbench.py longphases)
           PL.ptrace_stride = static_cast<int>(grid.x) | (static_cast<int>(grid.y) << 16);
           launch(verify_attn_long4_kernel<false, 128, true>, grid, dim3(256), s, PL);
@@ -2021,6 +2118,13 @@ static int verify_attention_impl(const void* q, int64_t q_stride, const void* k_
         }
       }
       if (traced) {
+      } else if (prefix_len > 0) {
+        if (d64)
+          launch(verify_attn_long4_kernel<false, 64, false, E, true>, grid, dim3(256), overlap ? side->stream : s, PL);
+        else if (kv8)
+          launch(verify_attn_long4_kernel<true, 128, false, E, true>, grid, dim3(256), overlap ? side->stream : s, PL);
+        else
+          launch(verify_attn_long4_kernel<false, 128, false, E, true>, grid, dim3(256), overlap ? side->stream : s, PL);
       } else if (d64)
         launch(verify_attn_long4_kernel<false, 64, false, E>, grid, dim3(256), overlap ? side->stream : s, PL);
       else if (kv8)
@@ -2048,12 +2152,16 @@ static int verify_attention_impl(const void* q, int64_t q_stride, const void* k_
     if (overlap) AIC_HIP_TRY(hipStreamWaitEvent(s, side->join, 0));
   }
   if ((rc = launch_ok("verify_attn_kernel")) != AIC_OK) return rc;
+  if (pside) {
+    AIC_HIP_TRY(hipStreamWaitEvent(s, pside->join, 0));
+    prefix_join.joined = true;
+  }
   if (P.direct && !P.mark_final) return AIC_OK;   // every row of the call is already final: no combine launch
   if (d64)
-    launch(verify_attn_combine_kernel<64, E>, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), s, P.ws_o, P.ws_ml, n_parts_total,
+    launch(verify_attn_combine_kernel<64, E>, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), s, ws_o_all, ws_ml_all, n_parts_total,
            static_cast<int>(rows), num_q_heads, static_cast<uint16_t*>(out), out_stride);
   else
-    launch(verify_attn_combine_kernel<128, E>, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), s, P.ws_o, P.ws_ml, n_parts_total,
+    launch(verify_attn_combine_kernel<128, E>, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), s, ws_o_all, ws_ml_all, n_parts_total,
            static_cast<int>(rows), num_q_heads, static_cast<uint16_t*>(out), out_stride);
   return launch_ok("verify_attn_combine_kernel");
 }
@@ -2084,6 +2192,50 @@ int aic_verify_attention_dt(const void* q, int64_t q_stride, const void* k_cache
                                          num_q_heads, num_kv_heads, head_size, block_size, sm_scale, out, out_stride,
                                          workspace, workspace_bytes, max_seq_len, short_reqs, n_short, long_reqs, n_long,
                                          sliding_window, sinks, stream);
+}
+
+// The same call for a step whose requests share their first shared_prefix_len tokens AND the pages that hold them (vLLM's
+// cascade attention: use_cascade / common_prefix_len of the metadata of the reference's one attention call,
+// arctic_inference/vllm/ulysses.py:510).  Keys [0, P), P = shared_prefix_len rounded down to the 32-token tile, are read
+// once for the step through prefix_block_table (prefix_attn.hip); the verify bodies take [P, ctx) of each request; one
+// combine launch merges both.  shared_prefix_len = 0 is aic_verify_attention_dt.  Not for stream capture.
+int aic_verify_attention_prefix(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache,
+                                int64_t block_stride, int kv_dtype, const float* k_scale, const float* v_scale,
+                                const int32_t* block_table, int max_blocks_per_seq, const int32_t* seq_lens,
+                                const int32_t* query_start_loc, int batch, int num_tokens, int max_q_len, int num_q_heads,
+                                int num_kv_heads, int head_size, int block_size, float sm_scale, void* out,
+                                int64_t out_stride, void* workspace, size_t workspace_bytes, int max_seq_len,
+                                const int32_t* short_reqs, int n_short, const int32_t* long_reqs, int n_long,
+                                int sliding_window, const float* sinks, int q_dtype, int shared_prefix_len,
+                                const int32_t* prefix_block_table, void* stream) {
+  AIC_REQUIRE(shared_prefix_len >= 0, "shared_prefix_len must be >= 0 (0 = none)");
+  AIC_REQUIRE(shared_prefix_len == 0 || prefix_block_table != nullptr, "a shared prefix needs prefix_block_table");
+  if (shared_prefix_len > 0 && sliding_window > 0) {
+    set_error("a shared prefix with a sliding window is not supported");
+    return AIC_ERR_UNSUPPORTED;
+  }
+  const int prefix_len = shared_prefix_len & ~(kTile - 1);
+  if (prefix_len == 0 || batch == 0 || num_tokens == 0)   // nothing for the prefix body: exactly the plain call
+    return aic_verify_attention_dt(q, q_stride, k_cache, v_cache, block_stride, kv_dtype, k_scale, v_scale, block_table,
+                                   max_blocks_per_seq, seq_lens, query_start_loc, batch, num_tokens, max_q_len, num_q_heads,
+                                   num_kv_heads, head_size, block_size, sm_scale, out, out_stride, workspace, workspace_bytes,
+                                   max_seq_len, short_reqs, n_short, long_reqs, n_long, sliding_window, sinks, q_dtype,
+                                   stream);
+  if (const int rc = attn_check_dtypes(q_dtype, kv_dtype); rc != AIC_OK) return rc;
+  AIC_REQUIRE(max_seq_len > shared_prefix_len, "every request must hold its query tokens behind the shared prefix "
+              "(max_seq_len %d, shared_prefix_len %d)", max_seq_len, shared_prefix_len);
+  const bool kv8 = kv_dtype == AIC_DT_FP8_E4M3;
+  if (q_dtype == AIC_DT_F16)
+    return verify_attention_impl<ElemF16>(q, q_stride, k_cache, v_cache, block_stride, kv8, k_scale, v_scale, block_table,
+                                          max_blocks_per_seq, seq_lens, query_start_loc, batch, num_tokens, max_q_len,
+                                          num_q_heads, num_kv_heads, head_size, block_size, sm_scale, out, out_stride,
+                                          workspace, workspace_bytes, max_seq_len, short_reqs, n_short, long_reqs, n_long,
+                                          sliding_window, sinks, stream, prefix_len, prefix_block_table);
+  return verify_attention_impl<ElemBf16>(q, q_stride, k_cache, v_cache, block_stride, kv8, k_scale, v_scale, block_table,
+                                         max_blocks_per_seq, seq_lens, query_start_loc, batch, num_tokens, max_q_len,
+                                         num_q_heads, num_kv_heads, head_size, block_size, sm_scale, out, out_stride,
+                                         workspace, workspace_bytes, max_seq_len, short_reqs, n_short, long_reqs, n_long,
+                                         sliding_window, sinks, stream, prefix_len, prefix_block_table);
 }
 
 // ---- a run of layers as one graph launch ------------------------------------------------------------------------------

@@ -246,20 +246,61 @@ def _attn_dtypes(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, 
     return qd, N.torch_dtype_code(k_cache.dtype)
 
 
+def _check_shared_prefix(shared_prefix_len: int, table: Optional[torch.Tensor], q: torch.Tensor, block_size: int,
+                         sliding_window: int, q_lens_host, seq_lens_host, seq_lens: torch.Tensor, max_seq_len: int) -> None:
+    """The argument rules of aic_verify_attention_prefix that can be told on the host.  ValueError before anything is
+    launched (and before the device check: none of this needs a GPU)."""
+    if shared_prefix_len < 0:
+        raise ValueError(f"shared_prefix_len must be >= 0, not {shared_prefix_len}")
+    if sliding_window > 0:
+        raise ValueError("a shared prefix is not served on a layer with a sliding window")
+    need = -(-shared_prefix_len // block_size)
+    if table is None:
+        raise ValueError("a shared prefix needs prefix_block_table (the pages of its tokens)")
+    if table.dtype != torch.int32 or table.dim() != 1 or not table.is_contiguous():
+        raise ValueError(f"prefix_block_table: contiguous int32 [n], not {table.dtype} {tuple(table.shape)}")
+    if table.numel() < need:
+        raise ValueError(f"prefix_block_table has {table.numel()} pages, {shared_prefix_len} tokens in pages of "
+                         f"{block_size} need {need}")
+    if table.device != q.device:
+        raise ValueError(f"prefix_block_table is on {table.device}, the call on {q.device}")
+    if max_seq_len <= shared_prefix_len:
+        raise ValueError(f"max_seq_len {max_seq_len} leaves no query token behind a shared prefix of {shared_prefix_len}")
+    if seq_lens_host is None and q_lens_host is not None and not seq_lens.is_cuda:
+        seq_lens_host = seq_lens.tolist()
+    if q_lens_host is not None and seq_lens_host is not None:
+        for i, (s, ql) in enumerate(zip(seq_lens_host, q_lens_host)):
+            if int(s) - int(ql) < shared_prefix_len:
+                raise ValueError(f"request {i}: seq_len {int(s)} - q_len {int(ql)} < shared_prefix_len {shared_prefix_len} "
+                                 "(every query token must lie behind the shared prefix)")
+
+
 def verify_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor,
                      seq_lens: torch.Tensor, query_start_loc: torch.Tensor, max_q_len: int, max_seq_len: int,
                      sm_scale: float, out: Optional[torch.Tensor] = None, num_splits_max: int = 64,
                      q_lens_host: Optional[Sequence[int]] = None, req_split=None,
                      k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None,
                      stream: Optional[int] = None, sliding_window: int = 0,
-                     sinks: Optional[torch.Tensor] = None) -> torch.Tensor:
+                     sinks: Optional[torch.Tensor] = None, shared_prefix_len: int = 0,
+                     prefix_block_table: Optional[torch.Tensor] = None,
+                     seq_lens_host: Optional[Sequence[int]] = None) -> torch.Tensor:
     """q [T, Hq, D] in bf16 or fp16 (token stride may exceed Hq*D: a view into an all-to-all receive buffer works),
     caches [num_blocks, block_size, Hkv, D] in q's dtype, or float8_e4m3fn with per-tensor `k_scale` / `v_scale`
     (device scalars, the scales A16 divided by); returns [T, Hq, D] in q's dtype (aic_verify_attention_dt).  `q_lens_host` (the per-request query
     lengths, which vLLM has on the host) lets long drafts take the shared-tile kernel.  `stream`: raw HIP stream
     handle (default: torch's current stream; a caller that issues one call per layer looks it up once).
-    `sliding_window` W > 0 / `sinks` f32 [Hq]: the per-layer features of gpt-oss-class models."""
+    `sliding_window` W > 0 / `sinks` f32 [Hq]: the per-layer features of gpt-oss-class models.
+    `shared_prefix_len` P > 0 with `prefix_block_table` (int32 [>= ceil(P / block_size)], contiguous, on q's device: the
+    pages of tokens 0 .. P - 1, e.g. `block_table[0]`): every request of the call begins with the same P tokens in the
+    same pages (prefix caching), and those keys are read once for the call (aic_verify_attention_prefix: cascade
+    attention) instead of once per request.  PRECONDITION: seq_len - q_len >= P for every request; checked here when the
+    lengths are on the host (`q_lens_host` together with `seq_lens_host`, or with a `seq_lens` that is a CPU tensor),
+    otherwise the caller's to keep.  Not with a sliding window.  0 (the default) is the call as it always was."""
     qd, kvd = _attn_dtypes(q, k_cache, v_cache, out)
+    shared_prefix_len = int(shared_prefix_len or 0)
+    if shared_prefix_len:
+        _check_shared_prefix(shared_prefix_len, prefix_block_table, q, int(k_cache.shape[1]), int(sliding_window or 0),
+                             q_lens_host, seq_lens_host, seq_lens, int(max_seq_len))
     _need_cuda(q, k_cache, v_cache, block_table, seq_lens, query_start_loc, sinks)
     if sinks is not None and (sinks.dtype != torch.float32 or sinks.numel() != q.shape[1] or not sinks.is_contiguous()):
         raise ValueError("sinks: contiguous float32, one value per query head")
@@ -274,6 +315,16 @@ def verify_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     if req_split is None and q_lens_host is not None:
         req_split = split_requests(q_lens_host, Hq // Hkv, q.device)
     short, n_short, long_, n_long = req_split if req_split is not None else (None, 0, None, 0)
+    if shared_prefix_len:
+        _need_cuda(prefix_block_table)
+        N.check(N.lib().aic_verify_attention_prefix(
+            q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(0), kvd, _ptr(k_scale),
+            _ptr(v_scale), block_table.data_ptr(), block_table.size(1), seq_lens.data_ptr(), query_start_loc.data_ptr(), B,
+            T, int(max_q_len), Hq, Hkv, D, bs, float(sm_scale), out.data_ptr(), out.stride(0), ws.data_ptr(), ws.numel(),
+            int(max_seq_len), _ptr(short) if n_short else None, n_short, _ptr(long_) if n_long else None, n_long, 0,
+            _ptr(sinks), qd, shared_prefix_len, prefix_block_table.data_ptr(),
+            N.current_stream_ptr() if stream is None else stream))
+        return out
     N.check(N.lib().aic_verify_attention_dt(
         q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(0), kvd, _ptr(k_scale),
         _ptr(v_scale), block_table.data_ptr(), block_table.size(1), seq_lens.data_ptr(), query_start_loc.data_ptr(), B, T,

@@ -158,3 +158,55 @@ def hip_sampler_ok(sm) -> bool:
     if getattr(sm, "min_tokens", None) or getattr(sm, "min_p", None) is not None:
         return False
     return bool(getattr(sm, "all_greedy", False)) or getattr(sm, "temperature", None) is not None
+
+
+SHARED_PREFIX_ENV = "ARCTIC_INFERENCE_HIP_SHARED_PREFIX"   # 1: cascade steps read their common prefix once (default off)
+# From where on the plugin hands a common prefix to aic_verify_attention_prefix.  The kernel's own floor is one 32-token
+# tile, and vLLM sets use_cascade from 256 common tokens and 8 requests on — but at those sizes the call LOSES: it adds a
+# launch, a stream fork / join and partials for every row.  Measured on the MI355X (tools/microbench.py prefix,
+# profiles/shared_prefix_microbench.txt; 4224-token contexts, 4 query tokens per request, time of the prefix call / time
+# of the plain call; "items" = requests x kv heads of this rank, what the plain call spreads over the chip):
+#   bf16 cache, 8 kv heads, 64 requests (512 items): P = 256 1.06, P = 1024 0.97, P = 2048 0.82
+#               8 kv heads, 32 requests (256 items), P = 2048: 0.90;  8 requests (64 items): 1.44
+#               1 kv head (a rank of SP = 8), 64 requests (64 items), P = 2048: 1.49
+#   fp8 cache,  8 kv heads, 64 requests (512 items): P = 256 1.12, P = 1024 1.06, P = 2048 0.90
+#               8 kv heads, 32 requests (256 items), P = 2048: 1.20;  8 requests (64 items): 1.93
+# So: the smallest measured length at which both cache kinds win, and the smallest measured item count at which each
+# cache kind wins there.  A rank of Ulysses SP = 8 with one kv head therefore needs 256 requests (512 with fp8): at the
+# 64 requests measured it loses, and is refused.
+SHARED_PREFIX_MIN_LEN = 2048
+SHARED_PREFIX_MIN_ITEMS = 256        # requests x local kv heads, bf16 / fp16 cache
+SHARED_PREFIX_MIN_ITEMS_FP8 = 512    # the same with an fp8 cache
+SHARED_PREFIX_FLOOR = 32             # below one tile the kernel serves nothing: never less than this, whatever the constants
+_MEASURED_KV_HEADS = 8               # a caller that does not name its kv heads is taken for the measured 8-head shape
+
+
+def shared_prefix_len(meta, window: int, capturing: bool, switch_on: bool, num_kv_heads: Optional[int] = None,
+                      fp8: bool = False) -> int:
+    """How many leading tokens of EVERY request of a verify call the HIP route reads once (ops.verify_attention's
+    `shared_prefix_len`), or 0 for the plain call: the whole decision, in one place.  vLLM 0.9.2's FlashAttentionMetadata
+    says so itself: `use_cascade` with `common_prefix_len` tokens whose pages are the leading columns of every
+    block-table row (field names recalled from 0.9.2; parity unpinned).  Taken only with the switch on,
+    on a layer without a sliding window, outside graph capture, from SHARED_PREFIX_MIN_LEN tokens (never fewer than 32),
+    with at least one query token behind the prefix (`max_seq_len`, where the metadata has it) and — where the metadata
+    carries `seq_lens` — from SHARED_PREFIX_MIN_ITEMS (fp8 cache: _FP8) requests x `num_kv_heads` (the layer's kv heads
+    on this rank) on.  Metadata without `seq_lens` has no request count to hold against that threshold: deliberately, the
+    length rule alone then decides (vLLM's metadata always carries it, so the plugin's own call is always counted).
+    Metadata without the cascade fields gives 0.  Correctness never depends on the answer: the block
+    table holds the shared pages either way."""
+    if not switch_on or capturing or int(window or 0) > 0:
+        return 0
+    if not getattr(meta, "use_cascade", False):
+        return 0
+    n = int(getattr(meta, "common_prefix_len", 0) or 0)
+    if n < max(SHARED_PREFIX_FLOOR, SHARED_PREFIX_MIN_LEN):
+        return 0
+    max_seq_len = getattr(meta, "max_seq_len", None)
+    if max_seq_len is not None and int(max_seq_len) <= n:
+        return 0
+    seq_lens = getattr(meta, "seq_lens", None)
+    if seq_lens is not None:
+        items = int(seq_lens.numel()) * int(num_kv_heads or _MEASURED_KV_HEADS)
+        if items < (SHARED_PREFIX_MIN_ITEMS_FP8 if fp8 else SHARED_PREFIX_MIN_ITEMS):
+            return 0
+    return n

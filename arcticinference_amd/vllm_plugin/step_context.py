@@ -20,11 +20,13 @@ PREFILL_ENV = "ARCTIC_INFERENCE_HIP_PREFILL"   # 1: steps with prefill chunks on
 _q_lens: Optional[np.ndarray] = None
 _shift_mode: bool = False
 _prefill_on: bool = False
+_shared_prefix_on: bool = False
 _splits: Dict[Tuple[int, int], object] = {}     # (group size, device index) -> ops.split_requests(...) of this step
 _step_splits: Dict[Tuple[int, int], object] = {}  # (group size, device index) -> ops.StepSplit of this step
 # attention calls routed to the HIP kernels (verify: all of them; prefill: those of them with prefill chunks) / left to
 # vLLM's backend
-calls = {"verify": 0, "fallback": 0, "prefill": 0}
+# shared_prefix: those of the verify calls that read a shared prompt prefix once (SHARED_PREFIX_ENV)
+calls = {"verify": 0, "fallback": 0, "prefill": 0, "shared_prefix": 0}
 
 
 def prefill_switch() -> bool:
@@ -32,10 +34,11 @@ def prefill_switch() -> bool:
 
 
 def publish(num_scheduled_tokens: np.ndarray, shift_mode: bool) -> None:
-    global _q_lens, _shift_mode, _prefill_on
+    global _q_lens, _shift_mode, _prefill_on, _shared_prefix_on
     _q_lens = np.asarray(num_scheduled_tokens)
     _shift_mode = bool(shift_mode)
     _prefill_on = prefill_switch()
+    _shared_prefix_on = shared_prefix_switch()
     _splits.clear()
     _step_splits.clear()
 
@@ -49,6 +52,16 @@ def clear() -> None:
 
 def prefill_on() -> bool:
     return _prefill_on
+
+
+def shared_prefix_switch() -> bool:
+    from .runner_logic import SHARED_PREFIX_ENV
+    return os.environ.get(SHARED_PREFIX_ENV, "0").strip().lower() in ("1", "true", "yes", "on")
+
+
+def shared_prefix_on() -> bool:
+    """ARCTIC_INFERENCE_HIP_SHARED_PREFIX as read when the step was published (default off)."""
+    return _shared_prefix_on
 
 
 def q_lens() -> Optional[np.ndarray]:

@@ -13,8 +13,9 @@ The group ALGEBRA is arcticinference_amd.ulysses.rank_groups() (pure, tested aga
 reshapes on CPU); this module only turns its rank lists into vLLM GroupCoordinators.  The attention patch is
 where this build differs from the reference on purpose: decode / verify steps (every request has at most
 MAX_SPEC_LEN + 1 query tokens) do not go to vLLM's attention backend but to aic_verify_attention_ex — and, with
-ARCTIC_INFERENCE_HIP_PREFILL=1, steps with prefill chunks go to aic_step_attention — and the copies around the
-all-to-alls are the fused HIP kernels of csrc/ulysses_pack.hip.
+ARCTIC_INFERENCE_HIP_PREFILL=1, steps with prefill chunks go to aic_step_attention; with
+ARCTIC_INFERENCE_HIP_SHARED_PREFIX=1, steps vLLM marks for cascade attention read their common prefix once
+(aic_verify_attention_prefix) — and the copies around the all-to-alls are the fused HIP kernels of csrc/ulysses_pack.hip.
 """
 from __future__ import annotations
 
@@ -25,7 +26,7 @@ import torch
 
 from ..ulysses import UlyssesAttention, rank_groups
 from . import step_context
-from .runner_logic import MAX_SPEC_LEN
+from .runner_logic import MAX_SPEC_LEN, shared_prefix_len
 
 
 def _flash_layout(kv_cache, num_kv_heads: int, head_size: int) -> bool:
@@ -306,12 +307,27 @@ def build_ulysses_patches():
                 ql = step_context.q_lens()
                 if ql is not None and len(ql) != batch:
                     split = None                               # the published step does not describe this call
+            # a cascade step (vLLM's use_cascade / common_prefix_len; ARCTIC_INFERENCE_HIP_SHARED_PREFIX): the common
+            # blocks are the leading columns of every block-table row, so row 0 is the prefix table
+            # (runner_logic.shared_prefix_len is the whole decision; what follows only keeps a table that is not what the
+            # field names promise — another dtype, too short — away from the call: every refusal is the plain call)
+            prefix = shared_prefix_len(meta, window, capturing, step_context.shared_prefix_on(), self.num_kv_heads, fp8)
+            prefix_table = None
+            if prefix:
+                prefix_table = meta.block_table[0]
+                if prefix_table.dtype != torch.int32 or prefix_table.numel() * k_cache.shape[1] < prefix:
+                    prefix, prefix_table = 0, None
+                elif not prefix_table.is_contiguous():         # a block table kept column-major or strided
+                    prefix_table = prefix_table.contiguous()
             ops.verify_attention(q, k_cache, v_cache, meta.block_table, meta.seq_lens.to(torch.int32),
                                  meta.query_start_loc.to(torch.int32), int(meta.max_query_len), int(meta.max_seq_len),
                                  float(self.impl.scale), out=out[:n].view(n, hq, D), req_split=split,
                                  k_scale=self._k_scale if fp8 else None, v_scale=self._v_scale if fp8 else None,
-                                 sliding_window=window, sinks=sinks)
+                                 sliding_window=window, sinks=sinks, shared_prefix_len=prefix,
+                                 prefix_block_table=prefix_table)
             step_context.calls["verify"] += 1
+            if prefix:
+                step_context.calls["shared_prefix"] += 1
             return out
 
         def _arctic_sinks(self):

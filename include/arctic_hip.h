@@ -198,6 +198,9 @@ int aic_debug_attn_light(int pct);
 /* debug aid: upper bound on the cross-workgroup split count of the long-draft part of a mixed call (0 = chosen by the
  * library); every setting computes the same result. */
 int aic_debug_attn_long_splits(int splits);
+/* debug aid: split count of the shared-prefix launch of aic_verify_attention_prefix (0 = chosen by the library; never more
+ * than the prefix has 32-token tiles or the workspace has slots); every setting computes the same result. */
+int aic_debug_attn_prefix_splits(int n);
 /* debug: which waves of a long-draft workgroup issue the tile DMA when the row tiles do not divide by four (0 = every wave its
  * quarter, 1 = the waves with one row tile more issue nothing, 2 = they keep their K pieces, 3 = wave 0 keeps one piece). */
 int aic_debug_attn_long_dma(int pattern);
@@ -492,6 +495,43 @@ int aic_verify_attention_dt(const void* q, int64_t q_stride, const void* k_cache
                             void* out, int64_t out_stride, void* workspace, size_t workspace_bytes,
                             int max_seq_len, const int32_t* short_reqs, int n_short, const int32_t* long_reqs,
                             int n_long, int sliding_window, const float* sinks, int q_dtype, void* stream);
+/* aic_verify_attention_dt for a step whose requests begin with the same tokens held in the same pages (prefix caching:
+ * an agent loop's system and tool prompt).  vLLM's FlashAttention backend serves such a step by cascade attention when
+ * the metadata of the step's one attention call (ulysses.py:510) says use_cascade / common_prefix_len; this is that
+ * call.  The shared keys are read once for the step instead of once per request:
+ *   prefix phase: every query row of the call against keys [0, P), non-causal, through prefix_block_table — a new body
+ *                 (csrc/prefix_attn.hip), its key range split over workgroups, un-normalised partials into the workspace;
+ *   suffix phase: the bodies of aic_verify_attention_dt on keys [P, seq_len_i) of each request, through block_table;
+ *   merge:        the combine launch of aic_verify_attention_dt over the partials of both (every row takes it: no
+ *                 direct output in such a call).
+ *   shared_prefix_len: tokens every request shares, >= 0.  0 (prefix_block_table may then be NULL) is exactly
+ *       aic_verify_attention_dt.  P = shared_prefix_len rounded DOWN to a multiple of 32: tokens [P, shared_prefix_len)
+ *       stay in the requests' own ranges (so a length below 32 is the plain call too).
+ *   prefix_block_table: device int32[ceil(shared_prefix_len / block_size)], the pages of tokens 0 .. shared_prefix_len - 1
+ *       (with vLLM: the leading columns of any row of block_table).  block_table must still be valid from column 0: the
+ *       suffix phase reads its columns from P / block_size on.
+ * PRECONDITION (not checked here — lengths are device data; arcticinference_amd.ops checks it when it has host lengths):
+ *   seq_len_i - q_len_i >= shared_prefix_len for every request, i.e. every query token lies behind the prefix.  A request
+ *   that breaks it gets rows that saw keys they should not; nothing is read out of bounds.
+ * Answered before any launch: shared_prefix_len < 0, a prefix without a table or max_seq_len <= shared_prefix_len are
+ * AIC_ERR_INVALID; sliding_window > 0 with shared_prefix_len > 0 is AIC_ERR_UNSUPPORTED (vLLM never cascades a windowed
+ * layer); dtype and head-size rules are those of aic_verify_attention_dt.  Sinks are allowed: they remain the start of a
+ * row's first SUFFIX partial and are counted once.
+ * Workspace: sized by aic_verify_attention_workspace_bytes as before; prefix and suffix split counts are fitted into what
+ * is given (at most 64 slots per row together, at least one each).
+ * The prefix launch runs beside the suffix launch on a stream the library owns, forked from and joined to `stream` by
+ * events inside the call: to the caller the call is ordered on `stream` like any other.
+ * Not for stream capture (the plugin does not use it while capturing).  Not served: aic_step_attention* (a step with
+ * prefill chunks ignores the prefix) and aic_verify_attention_layers. */
+int aic_verify_attention_prefix(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache,
+                                int64_t block_stride, int kv_dtype, const float* k_scale, const float* v_scale,
+                                const int32_t* block_table, int max_blocks_per_seq, const int32_t* seq_lens,
+                                const int32_t* query_start_loc, int batch, int num_tokens, int max_q_len,
+                                int num_q_heads, int num_kv_heads, int head_size, int block_size, float sm_scale,
+                                void* out, int64_t out_stride, void* workspace, size_t workspace_bytes,
+                                int max_seq_len, const int32_t* short_reqs, int n_short, const int32_t* long_reqs,
+                                int n_long, int sliding_window, const float* sinks, int q_dtype,
+                                int shared_prefix_len, const int32_t* prefix_block_table, void* stream);
 /* aic_verify_attention_ex for `n_layers` layers of one engine step in one call: k_caches / v_caches are HOST arrays of
  * device pointers (one cache pair per layer, same shape / dtype / strides), q and out advance by *_layer_stride elements
  * per layer (0: shared).  For drivers that own the whole step (arcticinference_amd/engine.py); inside vLLM attention is

@@ -106,6 +106,62 @@ def attn_dtypes(B=64, ctx=4096, qlen=4, Hq=32, Hkv=8, D=128, bs=16, layers=4, sp
           f"  fp16 / bf16 {med['fp16'] / med['bf16']:.3f}", flush=True)
 
 
+def attn_prefix(B=64, ctx=4224, P=2048, qlen=4, Hq=32, Hkv=8, D=128, bs=16, layers=4, kv8=False, rounds=5, iters=20):
+    """The same call with and without its shared prefix (ops.verify_attention(..., shared_prefix_len, prefix_block_table):
+    aic_verify_attention_prefix against aic_verify_attention_dt), alternating in ONE process as attn_dtypes does.  The first
+    P tokens of every request sit in the same pages (the leading block-table columns are equal), so both forms compute the
+    same thing; the plain one streams those pages once per request.  Prints each form's minimum / median / maximum, the
+    algorithmic KV bytes of both (partials not counted) with the rate each achieves, and the measured ratio of the medians
+    against the byte model (B (ctx - P) + P) / (B ctx)."""
+    ql = [qlen] * B
+    nblk = (ctx + bs - 1) // bs
+    n_sh = P // bs
+    nb = n_sh + B * (nblk - n_sh)
+    perm = torch.randperm(nb, device=dev).to(torch.int32)
+    bt = torch.empty(B, nblk, dtype=torch.int32, device=dev)
+    bt[:, :n_sh] = perm[:n_sh]
+    bt[:, n_sh:] = perm[n_sh:].view(B, nblk - n_sh)
+    table = bt[0, :n_sh].contiguous()
+    seq = torch.full((B,), ctx, dtype=torch.int32, device=dev)
+    qsl = torch.tensor(np.concatenate([[0], np.cumsum(ql)]).astype(np.int32), device=dev)
+    rs = ops.split_requests(ql, Hq // Hkv, dev)
+    kw = {}
+    if kv8:
+        kvs = []
+        for _ in range(layers):
+            raw = torch.randint(0, 256, (2, nb, bs, Hkv, D), dtype=torch.uint8, device=dev)
+            raw[(raw & 0x7f) == 0x7f] = 0x30
+            kvs.append(raw.view(torch.float8_e4m3fn))
+        sc = torch.full((1,), 0.02, dtype=torch.float32, device=dev)
+        kw = dict(k_scale=sc, v_scale=sc)
+    else:
+        kvs = [torch.randn(2, nb, bs, Hkv, D, device=dev, dtype=torch.bfloat16) for _ in range(layers)]
+    q = torch.randn(sum(ql), Hq, D, device=dev, dtype=torch.bfloat16)
+    outs = {name: torch.empty_like(q) for name in ("plain", "prefix")}
+    extra = {"plain": {}, "prefix": dict(shared_prefix_len=P, prefix_block_table=table)}
+    fns = {}
+    for name in outs:
+        def f(name=name, i=[0]):
+            kv = kvs[i[0] % layers]
+            i[0] += 1
+            ops.verify_attention(q, kv[0], kv[1], bt, seq, qsl, qlen, ctx, D ** -0.5, out=outs[name], req_split=rs, **kw,
+                                 **extra[name])
+        fns[name] = f
+    times = {name: [] for name in fns}
+    for _ in range(rounds):
+        for name, f in fns.items():
+            times[name].append(timeit(f, iters=iters))
+    diff = float((outs["plain"].float() - outs["prefix"].float()).abs().max())
+    med = {name: float(np.median(t)) for name, t in times.items()}
+    per_tok = 2 * Hkv * D * (1 if kv8 else 2)
+    mb = {"plain": B * ctx * per_tok / 1e6, "prefix": (B * (ctx - P) + P) * per_tok / 1e6}
+    print(f"prefix{' fp8kv' if kv8 else ''} B={B} ctx={ctx} P={P} qlen={qlen} Hq={Hq} Hkv={Hkv}: " +
+          "  ".join(f"{name} min {min(t):7.1f} med {med[name]:7.1f} max {max(t):7.1f} us  {mb[name]:6.1f} MB "
+                    f"{mb[name] / med[name]:5.2f} TB/s" for name, t in times.items()) +
+          f"  prefix / plain {med['prefix'] / med['plain']:.3f} (bytes {mb['prefix'] / mb['plain']:.3f})  max |diff| {diff:.2g}",
+          flush=True)
+
+
 def attn_mix(n_short=59, n_long=5, q_short=1, q_long=33, ctx=4224, Hq=32, Hkv=8, D=128, bs=16, layers=4, kv8=False):
     """The steady-state step of bench.py: most requests carry no draft (q_len 1), a few a long suffix draft — one call
     through the host-partitioned path (pair kernel) against its parts."""
@@ -591,6 +647,23 @@ if __name__ == "__main__":
         attn_dtypes(split=True, kv8=True)
         attn_dtypes(B=16, qlen=33, split=True, kv8=True)
         attn_dtypes(n_short=59, n_long=5, ctx=4224)          # attn_mix's step: the one-grid short + long launch
+    if "prefix" in what:     # a step's shared prompt prefix read once (cascade) against the plain call, alternating
+        for kv8 in (False, True):
+            for P in (256, 1024, 2048):
+                attn_prefix(B=64, P=P, kv8=kv8)
+            for B in (8, 32):
+                attn_prefix(B=B, P=2048, kv8=kv8)
+        attn_prefix(B=64, P=2048, Hq=4, Hkv=1)           # SP = 8 slice
+        attn_prefix(B=64, P=2048, qlen=1)                # a step without drafts
+        for B, P in ((8, 256), (16, 256), (8, 1024)):    # towards the break-even
+            attn_prefix(B=B, P=P)
+    if "prefixsplits" in what:   # split count of the prefix launch, forced (aic_debug_attn_prefix_splits)
+        for kv8 in (False, True):
+            for sp in (0, 1, 2, 4, 8, 16):
+                N.lib().aic_debug_attn_prefix_splits(sp)
+                print("prefix splits %2d: " % sp, end="")
+                attn_prefix(B=64, P=2048, kv8=kv8)
+        N.lib().aic_debug_attn_prefix_splits(0)
     if "long" in what:
         attn(B=16, qlen=33, split=True)
         attn(B=16, qlen=17, split=True)
