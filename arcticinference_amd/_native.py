@@ -138,6 +138,7 @@ _SIGNATURES = {
     "aic_mlp_set_embedding_rows": (c_int, [c_void_p, c_void_p]),
     "aic_lstm_destroy": (None, [c_void_p]),
     "aic_quantize_fp8_per_tensor": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "aic_lstm_max_rows": (c_int, []),
     "aic_lstm_padding_size": (c_int, [c_int]),
     "aic_lstm_propose": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "aic_debug_lstm_fused": (c_int, [c_int]),

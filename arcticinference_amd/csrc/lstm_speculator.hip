@@ -25,6 +25,8 @@
 //   * the LM head never materialises [B, V] logits: bf16-rounded logits are arg-max-reduced in the
 //     MFMA accumulator layout (4 regs -> 2 shuffles -> LDS across waves) to one (value, index) per
 //     workgroup and batch row.
+// Batches padded above 64 rows (65..256, aic_lstm_max_rows) take the wide body further down (wide_gemm_body: two weight
+// row tiles per wave) with the launch-boundary cell; everything up to 64 rows is as described here.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -1086,6 +1088,197 @@ __global__ void copy_tokens_kernel(const int32_t* __restrict__ src, int32_t* __r
   if (i < n) dst[i] = src[i];
 }
 
+// ---- wide GEMM: the same product for 65..256 batch rows (MT = 8 or 16 row tiles of 16) -------------
+// The narrow body keeps ONE 16-row weight tile per wave and reads one 1 KiB activation fragment from LDS per MFMA; at
+// 256 rows that is as much LDS time as HBM time, and its 2 x S x MT KiB staging (128 KiB at MT = 16) leaves one workgroup
+// per CU.  Here
+//   * a wave holds kWideRowTiles = 2 weight row tiles, so every activation fragment read from LDS feeds two MFMAs: per
+//     chunk and CU 128 KiB of ds_read_b128 (512 cycles at 256 B/clk) under 256 MFMAs per SIMD (1024 cycles at 16 each);
+//   * a chunk is S = 32 / MT k-steps, so the double-buffered staging is 64 KiB whatever MT is: two workgroups per CU,
+//     two waves per SIMD, <= 256 VGPRs + AGPRs per lane (the MT x 2 accumulators are 64 / 128 of them);
+//   * the weights are the SAME fragment-major copies (tile rt = 1 KiB per k-step, contiguous in k), streamed once from
+//     HBM into a ring of kWideRing register sets, kWideRing - 1 chunks ahead; a workgroup covers 4 x 2 x 16 = 128 weight rows;
+//   * activations stay xunit_bf16(m, k8, MT): a chunk is one contiguous S x MT KiB run, copied linearly into LDS.
+// Epilogues, bf16 rounding points and the arg-max tie rule are the narrow body's (lowest index at every level, rows
+// >= n_valid_rows masked); the per-block partials are best_val/best_idx[m][block] with 128-row blocks.
+// No workgroup waits for another one anywhere on the wide path (the cell runs as modes 0 + 1 across a launch boundary).
+constexpr int kMaxDraftRows = 256;     // native row cap (aic_lstm_max_rows): 16 row tiles
+constexpr int kWideRowTiles = 2;       // weight row tiles per wave
+constexpr int kWideTilesPerBlock = 4 * kWideRowTiles;
+constexpr int kWideRing = 4;
+
+template <int MT, int EPI>
+__device__ __forceinline__ void wide_gemm_body(const GemmArgs& A, uint4* __restrict__ lds, const int bx, const int by) {
+  static_assert(MT == 8 || MT == 16, "wide body: 128 or 256 padded rows");
+  constexpr int S = 32 / MT;               // k-steps per chunk
+  constexpr int RT = kWideRowTiles;
+  constexpr int BUF = S * MT * 64;         // uint4 per LDS buffer (32 KiB)
+  constexpr int XV = BUF / 256;            // uint4 per thread per activation chunk ( = 8 )
+  constexpr int RING = kWideRing;
+  const uint4* __restrict__ W = A.W;
+  const uint4* __restrict__ X = A.X;
+  const int n_rowtiles = A.n_rowtiles, steps_total = A.steps_total, steps_per_split = A.steps_per_split;
+
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int rt0 = (bx * 4 + wave) * RT;
+  const int split = by;
+  const int ks0 = split * steps_per_split;
+  const int n_chunks = steps_per_split / S;
+
+  static_assert(RT == 2, "two named weight streams per wave");
+  const uint4* const a_ptr0 = W + (static_cast<int64_t>(rt0 < n_rowtiles ? rt0 : 0) * steps_total + ks0) * 64 + lane;
+  const uint4* const a_ptr1 = W + (static_cast<int64_t>(rt0 + 1 < n_rowtiles ? rt0 + 1 : 0) * steps_total + ks0) * 64 + lane;
+  const uint4* const x_ptr = X + static_cast<int64_t>(ks0) * MT * 64 + tid;
+
+  f32x4 acc[RT][MT];
+#pragma unroll
+  for (int j = 0; j < RT; ++j)
+#pragma unroll
+    for (int i = 0; i < MT; ++i) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // the weight ring's indices are compile-time constants once the loops are unrolled and it stays in registers; the
+  // activation staging registers are named scalars: as an array they went to scratch (kernel-resource-usage remark)
+  static_assert(XV == 8, "eight staging registers");
+  uint4 a[RING][RT][S];
+  uint4 xr0, xr1, xr2, xr3, xr4, xr5, xr6, xr7;
+#define AIC_WIDE_LOAD_A(set_, c_)                                                                   \
+  _Pragma("unroll") for (int s_ = 0; s_ < S; ++s_) {                                                \
+    a[set_][0][s_] = ld_stream16(a_ptr0 + (static_cast<int64_t>(c_) * S + s_) * 64);                \
+    a[set_][1][s_] = ld_stream16(a_ptr1 + (static_cast<int64_t>(c_) * S + s_) * 64);                \
+  }
+#define AIC_WIDE_LOAD_X(c_)                                          \
+  {                                                                  \
+    const uint4* xp_ = x_ptr + static_cast<int64_t>(c_) * BUF;       \
+    xr0 = xp_[0];    xr1 = xp_[256];  xr2 = xp_[512];  xr3 = xp_[768];  \
+    xr4 = xp_[1024]; xr5 = xp_[1280]; xr6 = xp_[1536]; xr7 = xp_[1792]; \
+  }
+#define AIC_WIDE_STORE_X(buf_)                                       \
+  {                                                                  \
+    uint4* lp_ = lds + (buf_) * BUF + tid;                           \
+    lp_[0] = xr0;    lp_[256] = xr1;  lp_[512] = xr2;  lp_[768] = xr3;  \
+    lp_[1024] = xr4; lp_[1280] = xr5; lp_[1536] = xr6; lp_[1792] = xr7; \
+  }
+
+  AIC_WIDE_LOAD_X(0)
+#pragma unroll
+  for (int i = 0; i < RING - 1; ++i)
+    if (i < n_chunks) AIC_WIDE_LOAD_A(i, i)
+  AIC_WIDE_STORE_X(0)
+  __syncthreads();
+  for (int c0 = 0; c0 < n_chunks; c0 += RING) {
+#pragma unroll
+    for (int i = 0; i < RING; ++i) {
+      const int c = c0 + i;
+      if (c < n_chunks) {
+        if (c + 1 < n_chunks) AIC_WIDE_LOAD_X(c + 1)
+        if (c + RING - 1 < n_chunks) AIC_WIDE_LOAD_A((i + RING - 1) % RING, c + RING - 1)
+        const uint4* xb = lds + (c & 1) * BUF + lane;
+#pragma unroll
+        for (int s = 0; s < S; ++s)
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) {
+            const bf16x8 b = __builtin_bit_cast(bf16x8, xb[(s * MT + mt) * 64]);
+#pragma unroll
+            for (int j = 0; j < RT; ++j)
+              acc[j][mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a[i][j][s]), b, acc[j][mt], 0, 0, 0);
+          }
+        if (c + 1 < n_chunks) AIC_WIDE_STORE_X((c + 1) & 1)
+        __syncthreads();
+      }
+    }
+  }
+#undef AIC_WIDE_STORE_X
+#undef AIC_WIDE_LOAD_X
+#undef AIC_WIDE_LOAD_A
+
+  // accumulator layout (16x16): column (batch row) = lane & 15, weight row = (lane >> 4) * 4 + reg
+  if (EPI == 0) {
+#pragma unroll
+    for (int j = 0; j < RT; ++j) {
+      if (rt0 + j >= n_rowtiles) continue;
+      const int n0 = (rt0 + j) * 16 + (lane >> 4) * 4;
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) {
+        const int m = mt * 16 + (lane & 15);
+        const float4 v = make_float4(acc[j][mt][0], acc[j][mt][1], acc[j][mt][2], acc[j][mt][3]);
+        *reinterpret_cast<float4*>(A.part + (static_cast<int64_t>(split) * (MT * 16) + m) * A.n_cols_out + n0) = v;
+      }
+    }
+  } else {
+    // the K loop ended with a barrier: the staging buffers are free to carry the cross-wave reduction
+    float(*s_val)[MT * 16] = reinterpret_cast<float(*)[MT * 16]>(lds);
+    int(*s_idx)[MT * 16] = reinterpret_cast<int(*)[MT * 16]>(lds + BUF);
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+      float bv = -INFINITY;
+      int bi = 0x7fffffff;
+#pragma unroll
+      for (int j = 0; j < RT; ++j) {
+        const bool live = rt0 + j < n_rowtiles;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int n = (rt0 + j) * 16 + (lane >> 4) * 4 + e;
+          const float v = r(acc[j][mt][e]);  // logits are a bf16 tensor in the reference
+          if (live && n < A.n_valid_rows && (v > bv || (v == bv && n < bi))) {
+            bv = v;
+            bi = n;
+          }
+        }
+      }
+#pragma unroll
+      for (int off = 16; off <= 32; off <<= 1) {
+        const float ov = __shfl_xor(bv, off);
+        const int oi = __shfl_xor(bi, off);
+        if (ov > bv || (ov == bv && oi < bi)) {
+          bv = ov;
+          bi = oi;
+        }
+      }
+      if (lane < 16) {
+        s_val[wave][mt * 16 + lane] = bv;
+        s_idx[wave][mt * 16 + lane] = bi;
+      }
+    }
+    __syncthreads();
+    if (tid < MT * 16) {
+      float bv = s_val[0][tid];
+      int bi = s_idx[0][tid];
+      for (int w = 1; w < 4; ++w) {
+        const float ov = s_val[w][tid];
+        const int oi = s_idx[w][tid];
+        if (ov > bv || (ov == bv && oi < bi)) {
+          bv = ov;
+          bi = oi;
+        }
+      }
+      const int64_t n_blocks = (n_rowtiles + kWideTilesPerBlock - 1) / kWideTilesPerBlock;
+      A.best_val[tid * n_blocks + bx] = bv;
+      A.best_idx[tid * n_blocks + bx] = bi == 0x7fffffff ? 0x7fffffff : bi + A.row_offset;
+    }
+  }
+}
+
+template <int MT, int EPI>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
+wide_gemm_kernel(GemmArgs A) {
+  __shared__ uint4 lds[2 * 32 * 64];
+  wide_gemm_body<MT, EPI>(A, lds, blockIdx.x, blockIdx.y);
+}
+
+// skinny_pair_kernel's role for wide batches: workgroups [0, gate_bx * gate_by) run the gate projection of head h + 1,
+// the rest the LM head of head h
+template <int MT>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
+wide_pair_kernel(GemmArgs G, GemmArgs Hd, int gate_bx, int gate_by) {
+  __shared__ uint4 lds[2 * 32 * 64];
+  const int b = blockIdx.x, n_gate = gate_bx * gate_by;
+  if (b < n_gate)
+    wide_gemm_body<MT, 0>(G, lds, b % gate_bx, b / gate_bx);
+  else
+    wide_gemm_body<MT, 1>(Hd, lds, b - n_gate, 0);
+}
+
 }  // namespace aic
 
 using namespace aic;
@@ -1103,7 +1296,7 @@ struct aic_lstm {
   uint4 *x0 = nullptr, *h_bf16 = nullptr, *h_fp8 = nullptr;
   uint16_t* cell = nullptr;
   float* part = nullptr;
-  float* ss2_part = nullptr;   // [64][kCellParts] row-sum shares of the cell's parts
+  float* ss2_part = nullptr;   // [kMaxDraftRows][kCellParts] row-sum shares of the cell's parts
   unsigned int* sync = nullptr;   // [kSyncHeads][kSyncStride] slots of the one-launch cell (emptied by ln0_kernel)
   float* best_val = nullptr;
   int32_t* best_idx = nullptr;
@@ -1140,7 +1333,12 @@ struct aic_lstm {
   uint4* tmp_frag = nullptr;
 };
 
-static int pad_mt(int batch) { return batch <= 16 ? 1 : (batch <= 32 ? 2 : 4); }
+// padded row tiles of a batch: 1 / 2 / 4 take the skinny body, 8 / 16 (65..256 rows) the wide one
+static int pad_mt(int batch) { return batch <= 16 ? 1 : (batch <= 32 ? 2 : (batch <= 64 ? 4 : (batch <= 128 ? 8 : 16))); }
+// per-row candidates the LM head leaves in best_val / best_idx: one per 64-row block (skinny) or 128-row block (wide)
+static int head_blocks_of(const aic_lstm* m, int mt) {
+  return mt <= 4 ? m->head_blocks : (m->head_rowtiles + kWideTilesPerBlock - 1) / kWideTilesPerBlock;
+}
 
 template <bool FP8, int EPI>
 static int launch_gemm(int mt, dim3 grid, hipStream_t s, const uint4* W, const uint4* X, int rowtiles, int steps_total,
@@ -1149,6 +1347,18 @@ static int launch_gemm(int mt, dim3 grid, hipStream_t s, const uint4* W, const u
 #define AIC_GEMM(MT)                                                                                              \
   hipLaunchKernelGGL((skinny_gemm_kernel<FP8, MT, EPI>), grid, dim3(256), 0, s, W, X, rowtiles, steps_total,      \
                      steps_per_split, part, n_cols, x_scale, w_scale, n_valid, row_offset, bv, bi)
+  if (mt > 4) {
+    // wide batches: 128 weight rows per workgroup (the caller's grid.x counts 64-row blocks), bf16 only
+    AIC_REQUIRE(!FP8 && (mt == 8 || mt == 16), "no fp8 / %d-tile form of the wide GEMM", mt);
+    const GemmArgs A{W, X, rowtiles, steps_total, steps_per_split, part, n_cols, nullptr, 1.0f, n_valid, row_offset, bv, bi,
+                     nullptr};
+    const dim3 wgrid((rowtiles + kWideTilesPerBlock - 1) / kWideTilesPerBlock, grid.y);
+    if (mt == 8)
+      hipLaunchKernelGGL((wide_gemm_kernel<8, EPI>), wgrid, dim3(256), 0, s, A);
+    else
+      hipLaunchKernelGGL((wide_gemm_kernel<16, EPI>), wgrid, dim3(256), 0, s, A);
+    return launch_status("wide_gemm_kernel");
+  }
   if (mt == 1) AIC_GEMM(1);
   else if (mt == 2) AIC_GEMM(2);
   else AIC_GEMM(4);
@@ -1162,7 +1372,7 @@ static int run_mlp_lm_head(aic_lstm* m, int head_index, hipStream_t s, int64_t* 
   const aic_lstm_config& c = m->cfg;
   const int mt = m->cur_mt, mpad = mt * 16, B = m->cur_batch, Ds = c.inner_dim;
   int rc;
-  const bool fp8m = m->mlp_head8_t[head_index] && mpad <= c.head_fp8_max_batch;
+  const bool fp8m = m->mlp_head8_t[head_index] && mpad <= c.head_fp8_max_batch && mt <= 4;
   dim3 hgrid(m->head_blocks, 1);
   if (fp8m) {
     hipLaunchKernelGGL(quant_act_kernel, dim3(64), dim3(256), 0, s, m->h_bf16, m->h_fp8, m->amax + head_index, m->x_scale, Ds,
@@ -1176,7 +1386,7 @@ static int run_mlp_lm_head(aic_lstm* m, int head_index, hipStream_t s, int64_t* 
                                0, nullptr, 1.0f, c.vocab_size, c.vocab_offset, m->best_val, m->best_idx);
   }
   if (rc != AIC_OK) return rc;
-  hipLaunchKernelGGL(argmax_finish_kernel, dim3(mpad), dim3(256), 0, s, m->best_val, m->best_idx, m->head_blocks, mpad, B,
+  hipLaunchKernelGGL(argmax_finish_kernel, dim3(mpad), dim3(256), 0, s, m->best_val, m->best_idx, head_blocks_of(m, mt), mpad, B,
                      m->tokens, out_tokens, out_stride, out_col, out_vals);
   return launch_status("argmax_finish_kernel");
 }
@@ -1272,7 +1482,7 @@ static int run_head(aic_lstm* m, int head_index, hipStream_t s, int64_t* out_tok
                        mt, m->h_bf16, m->amax + head_index, m->ext_rows ? 1 : 0);
     if ((rc = launch_status("mlp_cell_kernel")) != AIC_OK) return rc;
     // 3. LM head + fused arg-max
-    const bool fp8m = m->mlp_head8_t[head_index] && mpad <= c.head_fp8_max_batch;
+    const bool fp8m = m->mlp_head8_t[head_index] && mpad <= c.head_fp8_max_batch && mt <= 4;
     dim3 hgrid(m->head_blocks, 1);
     if (fp8m) {
       hipLaunchKernelGGL(quant_act_kernel, dim3(64), dim3(256), 0, s, m->h_bf16, m->h_fp8, m->amax + head_index,
@@ -1286,7 +1496,7 @@ static int run_head(aic_lstm* m, int head_index, hipStream_t s, int64_t* out_tok
                                  nullptr, 0, nullptr, 1.0f, c.vocab_size, c.vocab_offset, m->best_val, m->best_idx);
     }
     if (rc != AIC_OK) return rc;
-    hipLaunchKernelGGL(argmax_finish_kernel, dim3(mpad), dim3(256), 0, s, m->best_val, m->best_idx, m->head_blocks, mpad,
+    hipLaunchKernelGGL(argmax_finish_kernel, dim3(mpad), dim3(256), 0, s, m->best_val, m->best_idx, head_blocks_of(m, mt), mpad,
                        B, m->tokens, out_tokens, out_stride, out_col, out_vals);
     return launch_status("argmax_finish_kernel");
   }
@@ -1312,7 +1522,7 @@ static int run_head(aic_lstm* m, int head_index, hipStream_t s, int64_t* out_tok
     if ((rc = launch_status("lstm_cell_kernel")) != AIC_OK) return rc;
   }
   // 3. LM head + fused arg-max
-  const bool fp8 = m->head8_t && mpad <= c.head_fp8_max_batch;
+  const bool fp8 = m->head8_t && mpad <= c.head_fp8_max_batch && mt <= 4;
   dim3 hgrid(m->head_blocks, 1);
   if (fp8) {
     hipLaunchKernelGGL(quant_act_kernel, dim3(64), dim3(256), 0, s, m->h_bf16, m->h_fp8, m->amax + head_index,
@@ -1325,12 +1535,14 @@ static int run_head(aic_lstm* m, int head_index, hipStream_t s, int64_t* out_tok
                                nullptr, 1.0f, c.vocab_size, c.vocab_offset, m->best_val, m->best_idx);
   }
   if (rc != AIC_OK) return rc;
-  hipLaunchKernelGGL(argmax_finish_kernel, dim3(mpad), dim3(256), 0, s, m->best_val, m->best_idx, m->head_blocks, mpad,
+  hipLaunchKernelGGL(argmax_finish_kernel, dim3(mpad), dim3(256), 0, s, m->best_val, m->best_idx, head_blocks_of(m, mt), mpad,
                      B, m->tokens, out_tokens, out_stride, out_col, out_vals);
   return launch_status("argmax_finish_kernel");
 }
 
 extern "C" {
+
+int aic_lstm_max_rows(void) { return kMaxDraftRows; }
 
 int aic_lstm_padding_size(int size) {  // arctic_speculator.py:39-44
   if (size <= 0) return size;
@@ -1366,8 +1578,8 @@ int aic_lstm_create(const aic_lstm_config* cfg, const aic_lstm_weights* w, aic_l
               4 * kCellMaxIter * 4 * kCellThreads);
   AIC_REQUIRE(cfg->input_hidden_dim > 0 && cfg->input_hidden_dim % 256 == 0,
               "input_hidden_dim must be a positive multiple of 256");
-  AIC_REQUIRE(cfg->vocab_size > 0 && cfg->n_predict > 0 && cfg->max_batch > 0 && cfg->max_batch <= 64,
-              "vocab_size / n_predict must be positive and max_batch in 1..64");
+  AIC_REQUIRE(cfg->vocab_size > 0 && cfg->n_predict > 0 && cfg->max_batch > 0 && cfg->max_batch <= kMaxDraftRows,
+              "vocab_size / n_predict must be positive and max_batch in 1..%d", kMaxDraftRows);
   AIC_REQUIRE(w->forget_emb && w->proj0 && w->proj1 && w->cell_ln_w && w->cell_ln_b && w->state_ln_w &&
                   w->state_ln_b && w->head,
               "missing weight pointer");
@@ -1399,7 +1611,7 @@ int aic_lstm_create(const aic_lstm_config* cfg, const aic_lstm_weights* w, aic_l
   AIC_ALLOC(m->h_fp8, static_cast<size_t>(mpad) * Ds);
   AIC_ALLOC(m->cell, static_cast<size_t>(mpad) * Ds * 2);
   AIC_ALLOC(m->part, static_cast<size_t>(m->gate_splits) * mpad * 4 * Ds * 4);
-  AIC_ALLOC(m->ss2_part, static_cast<size_t>(64) * kCellParts * sizeof(float));
+  AIC_ALLOC(m->ss2_part, static_cast<size_t>(kMaxDraftRows) * kCellParts * sizeof(float));
   AIC_ALLOC(m->sync, static_cast<size_t>(kSyncHeads) * kSyncStride * sizeof(unsigned int));
   AIC_HIP_TRY(hipMemset(m->sync, 0xff, static_cast<size_t>(kSyncHeads) * kSyncStride * sizeof(unsigned int)));
   AIC_ALLOC(m->best_val, static_cast<size_t>(m->head_blocks) * mpad * 4);
@@ -1446,8 +1658,8 @@ int aic_mlp_create(const aic_lstm_config* cfg, const aic_mlp_weights* w, aic_lst
   AIC_REQUIRE(cfg->inner_dim > 0 && cfg->inner_dim % 512 == 0, "inner_dim must be a positive multiple of 512");
   AIC_REQUIRE(cfg->input_hidden_dim > 0 && cfg->input_hidden_dim % 256 == 0,
               "input_hidden_dim must be a positive multiple of 256");
-  AIC_REQUIRE(cfg->vocab_size > 0 && cfg->n_predict > 0 && cfg->max_batch > 0 && cfg->max_batch <= 64,
-              "vocab_size / n_predict must be positive and max_batch in 1..64");
+  AIC_REQUIRE(cfg->vocab_size > 0 && cfg->n_predict > 0 && cfg->max_batch > 0 && cfg->max_batch <= kMaxDraftRows,
+              "vocab_size / n_predict must be positive and max_batch in 1..%d", kMaxDraftRows);
   AIC_REQUIRE(w->num_heads > 0 && w->num_heads <= 8, "an MLP speculator has 1..8 heads");
   for (int i = 0; i < w->num_heads; ++i)
     // emb[i] may be NULL: a vocab-sharded embedding is looked up by the caller (aic_mlp_set_embedding_rows)
@@ -1626,7 +1838,7 @@ int aic_lstm_head(aic_lstm* m, int head_index, const int32_t* last_tokens, int b
   AIC_REQUIRE(m && last_tokens && batch == m->cur_batch && head_index >= 0 && head_index < 64,
               "bad arguments to aic_lstm_head");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(copy_tokens_kernel, dim3(1), dim3(64), 0, s, last_tokens, m->tokens, batch);
+  hipLaunchKernelGGL(copy_tokens_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, last_tokens, m->tokens, batch);
   int rc = launch_status("copy_tokens_kernel");
   if (rc != AIC_OK) return rc;
   return run_head(m, head_index, s, out_tokens, 1, 0, out_vals);
@@ -1643,7 +1855,7 @@ static std::atomic<int> g_lstm_cell_launches{1};   // aic_debug_lstm_cell_launch
 static int propose_fused(aic_lstm* m, int k, int64_t* out_tokens, float* out_vals, hipStream_t s) {
   const aic_lstm_config& c = m->cfg;
   const int mt = m->cur_mt, mpad = mt * 16, B = m->cur_batch, Ds = c.inner_dim;
-  const bool fp8 = m->head8_t && mpad <= c.head_fp8_max_batch;
+  const bool fp8 = m->head8_t && mpad <= c.head_fp8_max_batch && mt <= 4;
   auto gate_args = [&](int head, int* splits_out) {
     const bool first = head == 0;
     const int K = first ? c.input_hidden_dim : Ds;
@@ -1679,11 +1891,13 @@ static int propose_fused(aic_lstm* m, int k, int64_t* out_tokens, float* out_val
   for (int h = 0; h < k; ++h) {
     CellArgs ca{m->part, splits, mpad, B, m->tokens, static_cast<const uint16_t*>(m->w.forget_emb), 0x7fffffff, m->alpha, Ds};
     PrevArgmax pa{};
-    if (h > 0) pa = PrevArgmax{m->best_val, m->best_idx, m->head_blocks, m->tokens, out_tokens, out_vals, k, h - 1};
+    if (h > 0) pa = PrevArgmax{m->best_val, m->best_idx, head_blocks_of(m, mt), m->tokens, out_tokens, out_vals, k, h - 1};
     // ONE cell launch per head (mode 2: row-sum and |max| steps inside the launch, the fp8 head's activations quantised from
     // registers): 4 x mpad workgroups of 256 threads, all resident at once.  Drafts of more than kSyncHeads heads, and
     // aic_debug_lstm_cell_launches(3), keep the three-launch form (mode 0, mode 1, quant_act_kernel).
-    const bool one_launch = g_lstm_cell_launches.load() == 1 && h < kSyncHeads && m->sync != nullptr;
+    // Batches padded above 64 rows keep the launch-boundary form too: 4 x mpad workgroups polling each other's slots would
+    // have to be resident together, and nothing on the wide path waits for another workgroup.
+    const bool one_launch = g_lstm_cell_launches.load() == 1 && h < kSyncHeads && m->sync != nullptr && mt <= 4;
     const uint16_t *clw = static_cast<const uint16_t*>(m->w.cell_ln_w), *clb = static_cast<const uint16_t*>(m->w.cell_ln_b);
     const uint16_t *slw = static_cast<const uint16_t*>(m->w.state_ln_w), *slb = static_cast<const uint16_t*>(m->w.state_ln_b);
     if (one_launch) {
@@ -1711,7 +1925,14 @@ static int propose_fused(aic_lstm* m, int k, int64_t* out_tokens, float* out_val
       const dim3 grid(static_cast<unsigned>(gate_bx * splits + m->head_blocks));
 #define AIC_PAIR(FP8H_, MT_, XQ_) \
   hipLaunchKernelGGL((skinny_pair_kernel<FP8H_, MT_, XQ_>), grid, dim3(256), 0, s, G, Hd, gate_bx, splits)
-      if (fp8 && xq) {
+      if (mt > 4) {
+        const int wgate_bx = (m->gate_rowtiles + kWideTilesPerBlock - 1) / kWideTilesPerBlock;
+        const dim3 wgrid(static_cast<unsigned>(wgate_bx * splits + head_blocks_of(m, mt)));
+        if (mt == 8)
+          hipLaunchKernelGGL((wide_pair_kernel<8>), wgrid, dim3(256), 0, s, G, Hd, wgate_bx, splits);
+        else
+          hipLaunchKernelGGL((wide_pair_kernel<16>), wgrid, dim3(256), 0, s, G, Hd, wgate_bx, splits);
+      } else if (fp8 && xq) {
         if (mt == 1) AIC_PAIR(true, 1, true); else AIC_PAIR(true, 2, true);
       } else if (fp8) {
         if (mt == 1) AIC_PAIR(true, 1, false); else AIC_PAIR(true, 2, false);
@@ -1738,7 +1959,7 @@ static int propose_fused(aic_lstm* m, int k, int64_t* out_tokens, float* out_val
       if (rc != AIC_OK) return rc;
     }
   }
-  hipLaunchKernelGGL(argmax_finish_kernel, dim3(mpad), dim3(256), 0, s, m->best_val, m->best_idx, m->head_blocks, mpad, B,
+  hipLaunchKernelGGL(argmax_finish_kernel, dim3(mpad), dim3(256), 0, s, m->best_val, m->best_idx, head_blocks_of(m, mt), mpad, B,
                      m->tokens, out_tokens, k, k - 1, out_vals);
   return launch_status("argmax_finish_kernel");
 }

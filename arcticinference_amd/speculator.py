@@ -11,7 +11,11 @@ All arithmetic runs in libarctic_hip.so (csrc/lstm_speculator.hip); this file ow
 distributed exchange and argument checking.  The k-head loop is one native call for tp_size == 1; it
 can be replayed as ONE HIP graph launch (`use_graph=True`, the reference's CUDA-graph cache, :806-842;
 keyed on the exact batch size here — see _replay_graph), which is NOT the default: measured slower than
-the eager launches on this runtime.
+the eager launches on this runtime.  Batches above 64 rows are never replayed from a graph, `use_graph` or not: they run
+the eager launches of the wide-GEMM schedule (the reference, too, runs eagerly past its graph sizes, :805).
+
+One native call drafts up to aic_lstm_max_rows() = 256 rows (65..256: wide GEMMs that read every weight byte once for
+all rows); a batch between that and padding_size(max_num_seqs) is drafted in even chunks (draft_chunks).
 """
 from __future__ import annotations
 
@@ -34,6 +38,23 @@ def padding_size(size: int) -> int:
     if mult < 1:
         return size
     return (size + mult - 1) // mult * mult
+
+
+def draft_chunks(batch: int, cap: int) -> List[int]:
+    """Row counts of the native calls that serve `batch` rows when one call serves at most `cap`: [batch] when it fits,
+    else n = ceil(batch / cap) EVEN chunks (sizes differ by at most one, larger first).  Even, because the LM-head
+    arithmetic is decided by the whole batch (above 32 padded rows the bf16 head, arctic_speculator.py:726-728): with
+    cap >= 65 every chunk of a batch above cap has more than 32 rows and takes the bf16 head like the batch it is cut
+    from, where a 14-row remainder would have taken the fp8 one."""
+    if batch <= cap:
+        return [batch]
+    n = -(-batch // cap)
+    q, rem = divmod(batch, n)
+    return [q + 1] * rem + [q] * (n - rem)
+
+
+def _native_max_rows() -> int:
+    return int(N.lib().aic_lstm_max_rows())
 
 
 def pad_vocab_size(vocab_size: int, pad_to: int = DEFAULT_VOCAB_PADDING_SIZE) -> int:
@@ -83,7 +104,10 @@ class ArcticLSTMSpeculator:
         self.quantize_lm_head = quantize_lm_head
         self.tp_size, self.tp_rank, self.tp_group = tp_size, tp_rank, tp_group
         self.device = torch.device(device)
-        self.max_batch = min(64, padding_size(max_num_seqs))
+        # capacity: what a caller may pass (the reference's padded static batch, :344); max_batch: rows of one native
+        # call (aic_lstm_max_rows() at most) — batches between the two are drafted in even chunks (draft_chunks)
+        self.capacity = padding_size(max_num_seqs)
+        self.max_batch = min(_native_max_rows(), self.capacity)
         self.use_graph = use_graph
         self._graphs: Dict[Tuple[int, int], object] = {}
         self.state_weight = 0.5 ** (0.5 / config.n_predict)
@@ -172,8 +196,8 @@ class ArcticLSTMSpeculator:
         if self._h is None:
             raise RuntimeError("load_weights() has not been called")
         B = input_ids.size(0)
-        if B > self.max_batch:
-            raise ValueError(f"batch {B} exceeds max_num_seqs padding {self.max_batch}")
+        if B > self.capacity:
+            raise ValueError(f"batch {B} exceeds max_num_seqs padding {self.capacity}")
         if not previous_hidden_states.is_cuda:
             raise RuntimeError("the speculator runs on the GPU only; there is no CPU fallback")
         k = num_predict_tokens
@@ -182,10 +206,26 @@ class ArcticLSTMSpeculator:
             hs = hs.to(torch.bfloat16).contiguous()
         toks = input_ids.to(torch.int32)
         hidx = None if hidden_index is None else hidden_index.to(torch.int32)
+        sizes = draft_chunks(B, self.max_batch)
+        if len(sizes) == 1:
+            return self._draft(toks, hs, hidx, B, k)
+        # above the native row cap: even chunks, each a draft of its own (rows of a draft do not interact; every chunk has
+        # more than 32 rows, so all of them take the bf16 head like the whole batch would)
+        outs, lo = [], 0
+        for n in sizes:
+            rows = slice(lo, lo + n)
+            outs.append(self._draft(toks[rows], hs if hidx is not None else hs[rows], None if hidx is None else hidx[rows],
+                                    n, k))
+            lo += n
+        return torch.cat(outs, dim=0)
+
+    def _draft(self, toks: torch.Tensor, hs: torch.Tensor, hidx: Optional[torch.Tensor], B: int, k: int) -> torch.Tensor:
+        """One draft of B <= max_batch rows.  `use_graph` replays a captured graph for batches up to 64 rows; wider ones
+        (the wide-GEMM schedule) always take the eager launches."""
         stream = N.current_stream_ptr()
         if self.tp_size == 1:
             out = torch.empty((B, k), dtype=torch.int64, device=self.device)
-            if self.use_graph and not torch.cuda.is_current_stream_capturing():
+            if self.use_graph and B <= 64 and not torch.cuda.is_current_stream_capturing():
                 return self._replay_graph(hs, hidx, toks, B, k)
             N.check(N.lib().aic_lstm_propose(self._h, hs.data_ptr(), _p(hidx), toks.data_ptr(), B, k, out.data_ptr(),
                                              None, stream))
@@ -314,7 +354,8 @@ class ArcticMLPSpeculator(ArcticLSTMSpeculator):
         self.quantize_lm_head = quantize_lm_head
         self.tp_size, self.tp_rank, self.tp_group = tp_size, tp_rank, tp_group
         self.device = torch.device(device)
-        self.max_batch = min(64, padding_size(max_num_seqs))
+        self.capacity = padding_size(max_num_seqs)
+        self.max_batch = min(_native_max_rows(), self.capacity)
         self.use_graph = use_graph
         self._graphs = {}
         self.state_weight = 0.5 ** (0.5 / config.n_predict)
@@ -425,22 +466,17 @@ class ArcticMLPSpeculator(ArcticLSTMSpeculator):
             N.check(N.lib().aic_mlp_set_embedding_rows(self._h, z.data_ptr()))
         return super().head_step(head, last_tokens, batch)
 
-    def generate_proposals(self, input_ids, previous_hidden_states, num_predict_tokens, hidden_index=None):
+    def _draft(self, toks, hs, hidx, B, k):
         if self.shard_embedding and self.tp_size == 1:
             # a sharded table on one rank (tests): the head loop with the lookup in front of every head
-            if num_predict_tokens > self.max_speculative_tokens:
-                raise ValueError(f"Max speculative tokens for model is {self.max_speculative_tokens}, but "
-                                 f"{num_predict_tokens} were requested")
-            B = input_ids.size(0)
-            hs = previous_hidden_states.to(torch.bfloat16).contiguous()
-            self.begin(hs, None if hidden_index is None else hidden_index.to(torch.int32), B)
-            last, outs = input_ids.to(torch.int32), []
-            for head in range(num_predict_tokens):
+            self.begin(hs, hidx, B)
+            last, outs = toks, []
+            for head in range(k):
                 tok, _ = self.head_step(head, last, B)
                 outs.append(tok.unsqueeze(1))
                 last = tok.to(torch.int32)
             return torch.cat(outs, dim=-1)
-        return super().generate_proposals(input_ids, previous_hidden_states, num_predict_tokens, hidden_index)
+        return super()._draft(toks, hs, hidx, B, k)
 
 
 def random_mlp_weights(cfg: MLPSpeculatorConfig, seed: int = 0, std: float = 0.02

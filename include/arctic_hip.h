@@ -342,7 +342,7 @@ typedef struct aic_lstm_config {
   int32_t inner_dim;         /* Ds == proj_dim == emb_dim (arctic_speculator.py:667-688) */
   int32_t n_predict;         /* used for state_weight = 0.5^(0.5/n_predict) (:575-577) */
   int32_t scale_input;       /* ln0 + 1/sqrt(2) on head 0 (:656-657) */
-  int32_t max_batch;         /* scratch sizing (padded batch) */
+  int32_t max_batch;         /* scratch sizing (padded batch), <= aic_lstm_max_rows() */
   int32_t head_fp8_max_batch;/* use the fp8 LM head when padded batch <= this (32, :726-728); 0 = never */
 } aic_lstm_config;
 
@@ -396,6 +396,10 @@ void aic_lstm_destroy(aic_lstm* m);
 /* per-tensor e4m3fn quantisation of a bf16 matrix: scale = amax/448, q = sat(x/scale)
  * (ops.scaled_fp8_quant with scale=None, fp8.py:207-210).  scale_out: device f32[1]. */
 int aic_quantize_fp8_per_tensor(const void* src_bf16, void* dst_fp8, float* scale_out, int64_t n, void* stream);
+/* The most batch rows one propose / begin / head call serves (256), hence the largest aic_lstm_config.max_batch.  The
+ * reference has no such cap: it replays graphs up to padding_size(max_num_seqs) and runs eagerly beyond
+ * (arctic_speculator.py:344, :805); callers split larger batches (speculator.py: draft_chunks). */
+int aic_lstm_max_rows(void);
 /* padding_size(): arctic_speculator.py:39-44 */
 int aic_lstm_padding_size(int batch);
 /* One call = the whole k-head draft loop on `stream` (no host sync, graph-capture safe):

@@ -487,6 +487,42 @@ def lstm(B, fp8=True):
     torch.cuda.empty_cache()
 
 
+def lstm_wide(sizes=(64, 96, 128, 192, 256), reps=5, iters=5):
+    """Batches above 64 rows (bf16 head, Llama-8B speculator shape, k = 3): one native call on the wide GEMMs against the
+    equivalent sequence of <= 64-row calls (draft_chunks(B, 64): what a 64-row cap would make of the batch, every weight
+    byte streamed once per call).  The two alternate in one process; median and max - min spread of the repetitions.
+    A width counts as served natively only if it wins by more than twice the larger spread."""
+    from arcticinference_amd.speculator import ArcticLSTMSpeculator, LSTMSpeculatorConfig, draft_chunks, random_lstm_weights
+    cfg = LSTMSpeculatorConfig(vocab_size=128256, input_hidden_dim=4096)
+    m = ArcticLSTMSpeculator(cfg, max_num_seqs=256, device=dev, quantize_lm_head=False, use_graph=False)
+    m.load_weights(random_lstm_weights(cfg, seed=0).items())
+    gb = 3 * (128256 * 4096 * 2 + 4 * 4096 * 4096 * 2) / 1e9          # algorithmic weight bytes of a k = 3 draft
+    for B in sizes:
+        hid = torch.randn(B, 4096, device=dev, dtype=torch.bfloat16)
+        ids = torch.randint(0, 128256, (B,), device=dev).to(torch.int32)
+        parts, lo = [], 0
+        for n in draft_chunks(B, 64):
+            parts.append((ids[lo:lo + n], hid[lo:lo + n], n))
+            lo += n
+        one = lambda: m._draft(ids, hid, None, B, 3)
+        seq = lambda: [m._draft(i, h, None, n, 3) for i, h, n in parts]
+        same = torch.equal(one(), torch.cat(seq()))
+        t_one, t_seq = [], []
+        for _ in range(reps):
+            t_one.append(timeit(one, iters=iters))
+            t_seq.append(timeit(seq, iters=iters))
+        med = lambda t: sorted(t)[len(t) // 2]
+        spread = max(max(t_one) - min(t_one), max(t_seq) - min(t_seq))
+        gain = med(t_seq) - med(t_one)
+        print(f"lstm wide B={B:3d}: one call {med(t_one):8.1f} us (spread {max(t_one) - min(t_one):6.1f}, "
+              f"{gb / med(t_one) * 1e3:5.2f} TB/s on {gb:.2f} GB)   {len(parts)} calls of <= 64 rows {med(t_seq):8.1f} us "
+              f"(spread {max(t_seq) - min(t_seq):6.1f})   gain {gain:8.1f} us vs bar {2 * spread:6.1f}: "
+              f"{'native' if len(parts) > 1 and gain > 2 * spread else ('same path' if len(parts) == 1 else 'NOT faster')}"
+              f"   same tokens: {same}", flush=True)
+    del m
+    torch.cuda.empty_cache()
+
+
 def rejection(B=64, k=3, V=128256):
     logits = torch.randn(B * k, V, device=dev, dtype=torch.bfloat16)
     draft = torch.randint(0, V, (B * k,), device=dev, dtype=torch.int32)
@@ -866,5 +902,7 @@ if __name__ == "__main__":
         lstm(64)
         lstm(32)
         lstm(8)
+    if "lstm" in what or "lstm_wide" in what:
+        lstm_wide()
     if "rej" in what:
         rejection()
