@@ -1140,6 +1140,430 @@ static int dispatch_sample(const void* logits, int dtype, int64_t row_stride, in
   }
 }
 
+// ================================================================================================
+// Token logprobs (aic_token_logprobs): vLLM 0.9.2's Sampler.compute_logprobs + gather_logprobs on the raw rows, for the
+// steps whose tokens the kernels above draw.  Launches over the grid (rows, S), the split of the sampler:
+//   first    per-segment (max, arg-max) partials and the count histogram of the keys' first digit;
+//   digit d  folds the previous histogram (the select of a top-k with k = n, on the raw values' keys: 16 bits for
+//            bf16 / fp16, 32 for f32) and counts digit d; the launch of digit 1 knows the row maximum m and the selected
+//            token's value, so the fixed-point sum of exp(x - m) and the rank count ride in it;
+//   gather   everything above the cut value, and the ties at it from the lowest index up, into <= 32 candidate slots
+//            (slot order is arbitrary: an integer atomic hands them out);
+//   finish   one wavefront per row: folds the partials, orders the candidates by (value descending, index ascending)
+//            and writes the row's outputs.
+// n = 0 needs no select: first, the sum launch, finish: 2 passes over the row.  With n > 0 a bf16 / fp16 row is read 3
+// times (first, digit 1, gather) and an f32 row 5 times; aic_sample_topk_topp with both filters on reads either 10 times.
+// ================================================================================================
+constexpr int kLogprobsMax = 32;
+enum { kLpFirst = 0, kLpDigit = 1, kLpGather = 2 };
+
+struct LpState {
+  uint32_t prefix;  // the cut key's digits chosen so far
+  uint32_t krem;    // n minus the entries above the prefix's range
+};
+
+struct LpArgs {
+  const void* logits;
+  int64_t row_stride;
+  const int64_t* row_index;
+  const int32_t* token_ids;
+  float* part_val;     // [rows][n_splits] per-segment maximum
+  int32_t* part_idx;   //                  and its lowest index
+  u64* seg_sum;        // [rows][n_splits] sum exp(x - m) in 2^-40 units
+  int32_t* seg_ge;     // [rows][n_splits] #{x >= x_token}
+  LpState* state;      // [digits + 1][rows], entry L written by launch L
+  uint32_t* cnt;       // [2][rows][n_splits][256]
+  int32_t* cand_n;     // [rows]
+  float* cand_val;     // [rows][kLogprobsMax]
+  int32_t* cand_idx;
+  int rows, vocab, seg_len, n_splits, n;
+  int launch;          // kLpDigit: this pass's digit; kLpGather: the number of digits
+  int with_sum, with_hist;
+};
+
+__device__ __forceinline__ u64 wave_sum_u64(u64 x) {
+  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+  return x;
+}
+
+template <typename T, int KIND, bool VEC_OK>
+__global__ void __launch_bounds__(256) logprobs_row_kernel(LpArgs a) {
+  constexpr int BITS = KeyOf<T>::kBits;
+  const int row = blockIdx.x;
+  const int seg = blockIdx.y;
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int begin = seg * a.seg_len;
+  const int end = min(begin + a.seg_len, a.vocab);
+  const T* base = static_cast<const T*>(a.logits) + (a.row_index ? a.row_index[row] : static_cast<int64_t>(row)) * a.row_stride;
+
+  __shared__ u64 s_c[256];        // folded histogram of the previous launch
+  __shared__ uint32_t s_hc[256];  // this block's histogram
+  __shared__ LpState s_st;
+  __shared__ float s_m;
+  __shared__ int s_need, s_here;
+  __shared__ int s_w[4];
+  __shared__ float s_v[4];
+  __shared__ int s_i[4];
+  __shared__ u64 s_q[4];
+
+  if (KIND == kLpFirst) {
+    if (a.with_hist) s_hc[tid] = 0;
+    __syncthreads();
+    Best best;
+    best.v = -INFINITY;
+    best.i = begin;
+    int cur = -1;
+    uint32_t cc = 0;
+    for_each_elem<T, VEC_OK>(base, begin, end, [&](int idx, float l) {
+      if (l > best.v) {
+        best.v = l;
+        best.i = idx;
+      }
+      if (a.with_hist) {
+        const int b = key_of<T>(l) >> (BITS - 8);
+        if (b != cur) {
+          if (cur >= 0) atomicAdd(&s_hc[cur], cc);
+          cur = b;
+          cc = 0;
+        }
+        ++cc;
+      }
+    });
+    if (cur >= 0) atomicAdd(&s_hc[cur], cc);
+    best = wave_best(best);
+    if (lane == 0) {
+      s_v[wave] = best.v;
+      s_i[wave] = best.i;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      Best b;
+      b.v = s_v[0];
+      b.i = s_i[0];
+      for (int w = 1; w < 4; ++w) {
+        Best o;
+        o.v = s_v[w];
+        o.i = s_i[w];
+        b = better(b, o);
+      }
+      a.part_val[row * a.n_splits + seg] = b.v;
+      a.part_idx[row * a.n_splits + seg] = b.i;
+      if (seg == 0) a.cand_n[row] = 0;
+    }
+    if (a.with_hist)
+      a.cnt[(static_cast<size_t>(row) * a.n_splits + seg) * 256 + tid] = s_hc[tid];
+    return;
+  }
+
+  // ---- the row's maximum; the select state after the previous launch's histogram
+  const int L = a.launch;
+  if (tid < 64) {
+    Best b;
+    b.v = -INFINITY;
+    b.i = INT_MAX;
+    for (int s = tid; s < a.n_splits; s += 64) {
+      Best o;
+      o.v = a.part_val[row * a.n_splits + s];
+      o.i = a.part_idx[row * a.n_splits + s];
+      b = better(b, o);
+    }
+    b = wave_best(b);
+    if (tid == 0) s_m = b.v;
+  }
+  const size_t prev_hist = (static_cast<size_t>((L - 1) & 1) * a.rows + row) * a.n_splits * 256;
+  if (a.n > 0) {
+    u64 c = 0;
+    for (int s = 0; s < a.n_splits; ++s) c += a.cnt[prev_hist + static_cast<size_t>(s) * 256 + tid];
+    s_c[tid] = c;
+    if (tid == 0) {
+      LpState st;
+      st.prefix = 0;
+      st.krem = static_cast<uint32_t>(a.n);
+      if (L > 1) st = a.state[static_cast<size_t>(L - 1) * a.rows + row];
+      s_st = st;
+    }
+  }
+  __syncthreads();
+  if (a.n > 0) {
+    if (tid < 64) {  // the bin of the n-th largest key, counting from the top
+      LpState st = s_st;
+      const Sel s = select_bin(s_c, false, static_cast<u64>(st.krem) - 1);
+      st.prefix |= static_cast<uint32_t>(s.bin) << digit_shift(BITS, L - 1);
+      st.krem -= static_cast<uint32_t>(s.before);
+      if (tid == 0) {
+        s_st = st;
+        if (KIND == kLpDigit && seg == 0) a.state[static_cast<size_t>(L) * a.rows + row] = st;
+        if (KIND == kLpGather) {  // the cut value's ties: how many the earlier segments hold, and this one
+          const size_t hb = prev_hist + (st.prefix & 0xFF);
+          u64 before = 0;
+          for (int s2 = 0; s2 < seg; ++s2) before += a.cnt[hb + static_cast<size_t>(s2) * 256];
+          s_here = static_cast<int>(a.cnt[hb + static_cast<size_t>(seg) * 256]);
+          s_need = before >= st.krem ? 0 : static_cast<int>(st.krem - before);
+        }
+      }
+    }
+    __syncthreads();
+  }
+  const float m = s_m;
+
+  if (KIND == kLpDigit) {
+    float xtok = m;  // token_ids == NULL: the arg-max
+    if (a.token_ids) {
+      const int tok = a.token_ids[row];
+      xtok = (tok >= 0 && tok < a.vocab) ? Elem<T>::get(base, tok) : NAN;  // never indexed out of the row
+    }
+    const uint32_t prefix = s_st.prefix;
+    const int sh = digit_shift(BITS, L);
+    if (a.with_hist) s_hc[tid] = 0;
+    __syncthreads();
+    u64 acc = 0;
+    int ge = 0;
+    int cur = -1;
+    uint32_t cc = 0;
+    for_each_elem<T, VEC_OK>(base, begin, end, [&](int idx, float l) {
+      (void)idx;
+      if (a.with_sum) {
+        if (l > -INFINITY) acc += fixed_mass(expf(l - m));
+        ge += l >= xtok;
+      }
+      if (a.with_hist) {
+        const uint32_t key = key_of<T>(l);
+        if (!prefix_match(key, prefix, BITS, L)) return;
+        const int b = (key >> sh) & 0xFF;
+        if (b != cur) {
+          if (cur >= 0) atomicAdd(&s_hc[cur], cc);
+          cur = b;
+          cc = 0;
+        }
+        ++cc;
+      }
+    });
+    if (cur >= 0) atomicAdd(&s_hc[cur], cc);
+    if (a.with_sum) {
+      acc = wave_sum_u64(acc);
+      for (int off = 32; off > 0; off >>= 1) ge += __shfl_xor(ge, off);
+      if (lane == 0) {
+        s_q[wave] = acc;
+        s_w[wave] = ge;
+      }
+    }
+    __syncthreads();
+    if (a.with_sum && tid == 0) {
+      a.seg_sum[row * a.n_splits + seg] = s_q[0] + s_q[1] + s_q[2] + s_q[3];
+      a.seg_ge[row * a.n_splits + seg] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    }
+    if (a.with_hist)
+      a.cnt[((static_cast<size_t>(L & 1) * a.rows + row) * a.n_splits + seg) * 256 + tid] = s_hc[tid];
+    return;
+  }
+
+  // ---- gather: the entries above the cut value tau, and tau's ties from the lowest index up
+  const uint32_t tau = s_st.prefix;
+  const int need = s_need, here = s_here;
+  auto push = [&](int idx, float l) {
+    const int slot = atomicAdd(&a.cand_n[row], 1);
+    if (slot < kLogprobsMax) {
+      a.cand_val[row * kLogprobsMax + slot] = l;
+      a.cand_idx[row * kLogprobsMax + slot] = idx;
+    }
+  };
+  if (need > 0 && need < here) {
+    // the cut falls inside this segment's ties: rank them in index order (8 contiguous elements per thread)
+    const int n_iter = (end - begin + 2047) / 2048;
+    int seen = 0;
+    for (int it = 0; it < n_iter; ++it) {
+      const int i0 = begin + it * 2048 + tid * 8;
+      float lv[8];
+      int c = 0;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        lv[e] = i0 + e < end ? Elem<T>::get(base, i0 + e) : 0.0f;
+        if (i0 + e < end && key_of<T>(lv[e]) == tau) ++c;
+      }
+      int total;
+      int rank = seen + block_excl_scan(c, s_w, &total);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        if (i0 + e >= end) continue;
+        const uint32_t key = key_of<T>(lv[e]);
+        if (key > tau) {
+          push(i0 + e, lv[e]);
+        } else if (key == tau) {
+          if (rank < need) push(i0 + e, lv[e]);
+          ++rank;
+        }
+      }
+      seen += total;
+    }
+  } else {
+    const bool take_ties = need > 0;  // need >= here: every tie of this segment is inside the cut
+    for_each_elem<T, VEC_OK>(base, begin, end, [&](int idx, float l) {
+      const uint32_t key = key_of<T>(l);
+      if (key > tau || (key == tau && take_ties)) push(idx, l);
+    });
+  }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(64)
+logprobs_finish_kernel(LpArgs a, int32_t* __restrict__ out_ids, float* __restrict__ out_lp, int64_t* __restrict__ out_rank) {
+  const int row = blockIdx.x;
+  const int lane = threadIdx.x;
+  Best b;
+  b.v = -INFINITY;
+  b.i = INT_MAX;
+  u64 sum = 0;
+  long long ge = 0;
+  for (int s = lane; s < a.n_splits; s += 64) {
+    Best o;
+    o.v = a.part_val[row * a.n_splits + s];
+    o.i = a.part_idx[row * a.n_splits + s];
+    b = better(b, o);
+    sum += a.seg_sum[row * a.n_splits + s];
+    ge += a.seg_ge[row * a.n_splits + s];
+  }
+  b = wave_best(b);
+  sum = wave_sum_u64(sum);
+  ge = static_cast<long long>(wave_sum_u64(static_cast<u64>(ge)));
+  const float m = b.v;
+  const float log_s = logf(static_cast<float>(static_cast<double>(sum) * kMassUnit));
+  const int cols = 1 + a.n;
+  if (lane == 0) {
+    int tok = b.i;
+    float xtok = m;
+    if (a.token_ids) {
+      const T* base = static_cast<const T*>(a.logits) + (a.row_index ? a.row_index[row] : static_cast<int64_t>(row)) * a.row_stride;
+      tok = a.token_ids[row];
+      xtok = (tok >= 0 && tok < a.vocab) ? Elem<T>::get(base, tok) : NAN;
+    }
+    out_ids[static_cast<size_t>(row) * cols] = tok;
+    out_lp[static_cast<size_t>(row) * cols] = (xtok - m) - log_s;
+    out_rank[row] = ge;
+  }
+  if (a.n == 0) return;
+  // order the candidates: position = how many of the others come first (value descending, index ascending)
+  const int cn = min(a.cand_n[row], a.n);
+  Best c;
+  c.v = -INFINITY;
+  c.i = INT_MAX;
+  if (lane < cn) {
+    c.v = a.cand_val[row * kLogprobsMax + lane];
+    c.i = a.cand_idx[row * kLogprobsMax + lane];
+  }
+  int pos = 0;
+  for (int k = 0; k < cn; ++k) {
+    const float vk = __shfl(c.v, k);
+    const int ik = __shfl(c.i, k);
+    pos += (vk > c.v) || (vk == c.v && ik < c.i);
+  }
+  if (lane < cn) {
+    out_ids[static_cast<size_t>(row) * cols + 1 + pos] = c.i;
+    out_lp[static_cast<size_t>(row) * cols + 1 + pos] = (c.v - m) - log_s;
+  } else if (lane < a.n) {  // fewer than n entries can only come from NaN logits, which are outside the contract
+    out_ids[static_cast<size_t>(row) * cols + 1 + lane] = -1;
+    out_lp[static_cast<size_t>(row) * cols + 1 + lane] = NAN;
+  }
+}
+
+static size_t lp_align(size_t x) { return (x + 255) / 256 * 256; }
+
+static size_t logprobs_workspace_bytes(int rows, int vocab) {
+  int seg_len, n_splits;
+  split_geometry(rows, vocab, &seg_len, &n_splits);
+  const size_t r = static_cast<size_t>(rows > 0 ? rows : 1);
+  return lp_align(r * kMaxSplits * sizeof(u64)) + lp_align(5 * r * sizeof(LpState)) +
+         3 * lp_align(r * kMaxSplits * sizeof(int32_t)) + lp_align(r * sizeof(int32_t)) +
+         2 * lp_align(r * kLogprobsMax * sizeof(int32_t)) +
+         lp_align(2 * r * static_cast<size_t>(n_splits) * 256 * sizeof(uint32_t)) + 256;
+}
+
+template <typename T>
+static int run_logprobs(const void* logits, int64_t row_stride, int vocab, const int64_t* row_index,
+                        const int32_t* token_ids, int rows, int n, int32_t* out_ids, float* out_lp, int64_t* out_rank,
+                        void* workspace, hipStream_t stream) {
+  LpArgs a;
+  split_geometry(rows, vocab, &a.seg_len, &a.n_splits);
+  const size_t r = static_cast<size_t>(rows);
+  char* p = static_cast<char*>(workspace);
+  auto carve = [&](size_t bytes) {
+    char* q = p;
+    p += lp_align(bytes);
+    return q;
+  };
+  a.seg_sum = reinterpret_cast<u64*>(carve(r * kMaxSplits * sizeof(u64)));
+  a.state = reinterpret_cast<LpState*>(carve(5 * r * sizeof(LpState)));
+  a.part_val = reinterpret_cast<float*>(carve(r * kMaxSplits * sizeof(float)));
+  a.part_idx = reinterpret_cast<int32_t*>(carve(r * kMaxSplits * sizeof(int32_t)));
+  a.seg_ge = reinterpret_cast<int32_t*>(carve(r * kMaxSplits * sizeof(int32_t)));
+  a.cand_n = reinterpret_cast<int32_t*>(carve(r * sizeof(int32_t)));
+  a.cand_val = reinterpret_cast<float*>(carve(r * kLogprobsMax * sizeof(float)));
+  a.cand_idx = reinterpret_cast<int32_t*>(carve(r * kLogprobsMax * sizeof(int32_t)));
+  a.cnt = reinterpret_cast<uint32_t*>(carve(2 * r * static_cast<size_t>(a.n_splits) * 256 * sizeof(uint32_t)));
+  a.logits = logits;
+  a.row_stride = row_stride;
+  a.row_index = row_index;
+  a.token_ids = token_ids;
+  a.rows = rows;
+  a.vocab = vocab;
+  a.n = n;
+  const bool vec_ok = (reinterpret_cast<uintptr_t>(logits) % 16 == 0) && ((row_stride * sizeof(T)) % 16 == 0);
+  const dim3 grid(rows, a.n_splits);
+  auto go = [&](int kind, int launch, bool with_sum, bool with_hist) -> int {
+    a.launch = launch;
+    a.with_sum = with_sum;
+    a.with_hist = with_hist;
+#define AIC_LP_LAUNCH(K)                                                                          \
+  if (vec_ok)                                                                                     \
+    hipLaunchKernelGGL((logprobs_row_kernel<T, K, true>), grid, dim3(256), 0, stream, a);         \
+  else                                                                                            \
+    hipLaunchKernelGGL((logprobs_row_kernel<T, K, false>), grid, dim3(256), 0, stream, a);
+    if (kind == kLpFirst) {
+      AIC_LP_LAUNCH(kLpFirst)
+    } else if (kind == kLpDigit) {
+      AIC_LP_LAUNCH(kLpDigit)
+    } else {
+      AIC_LP_LAUNCH(kLpGather)
+    }
+#undef AIC_LP_LAUNCH
+    return launch_status("logprobs_row_kernel");
+  };
+  constexpr int digits = KeyOf<T>::kBits / 8;
+  int rc = go(kLpFirst, 0, false, n > 0);
+  if (rc == AIC_OK) rc = go(kLpDigit, 1, true, n > 0);
+  if (n > 0) {
+    for (int d = 2; d < digits && rc == AIC_OK; ++d) rc = go(kLpDigit, d, false, true);
+    if (rc == AIC_OK) rc = go(kLpGather, digits, false, false);
+  }
+  if (rc != AIC_OK) return rc;
+  hipLaunchKernelGGL((logprobs_finish_kernel<T>), dim3(rows), dim3(64), 0, stream, a, out_ids, out_lp, out_rank);
+  return launch_status("logprobs_finish_kernel");
+}
+
+static int dispatch_logprobs(const void* logits, int dtype, int64_t row_stride, int vocab, const int64_t* row_index,
+                             const int32_t* token_ids, int rows, int n, int32_t* out_ids, float* out_lp,
+                             int64_t* out_rank, void* ws, void* stream) {
+  AIC_REQUIRE(n >= 0 && n <= kLogprobsMax, "num_logprobs %d outside 0 .. %d", n, kLogprobsMax);
+  if (dtype != AIC_DT_F32 && dtype != AIC_DT_BF16 && dtype != AIC_DT_F16) {
+    set_error("unsupported logits dtype %d", dtype);
+    return AIC_ERR_UNSUPPORTED;
+  }
+  if (rows == 0) return AIC_OK;
+  AIC_REQUIRE(rows > 0 && vocab > 0 && row_stride >= 0, "bad arguments to the logprobs call");
+  AIC_REQUIRE(n <= vocab, "num_logprobs %d exceeds the vocabulary %d", n, vocab);
+  AIC_REQUIRE(logits && out_ids && out_lp && out_rank && ws, "null logits / outputs / workspace");
+  AIC_NEED_DEVICE();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (dtype) {
+    case AIC_DT_F32:
+      return run_logprobs<float>(logits, row_stride, vocab, row_index, token_ids, rows, n, out_ids, out_lp, out_rank, ws, s);
+    case AIC_DT_BF16:
+      return run_logprobs<bf16_t>(logits, row_stride, vocab, row_index, token_ids, rows, n, out_ids, out_lp, out_rank, ws, s);
+    default:
+      return run_logprobs<f16_t>(logits, row_stride, vocab, row_index, token_ids, rows, n, out_ids, out_lp, out_rank, ws, s);
+  }
+}
+
 }  // namespace aic
 
 using namespace aic;
@@ -1201,6 +1625,21 @@ int aic_sample_topk_topp(const void* logits, int logits_dtype, int64_t row_strid
                          int rows, int32_t* out_token_ids, void* workspace, void* stream) {
   return dispatch_sample(logits, logits_dtype, row_stride, vocab, row_index, temperature, exp_noise, top_k, top_p, rows,
                          out_token_ids, workspace, stream);
+}
+
+int aic_logprobs_max(void) { return kLogprobsMax; }
+
+size_t aic_logprobs_workspace_bytes(int rows, int vocab, int logits_dtype, int num_logprobs) {
+  (void)logits_dtype;  // the key width and n change the number of passes, not the state
+  (void)num_logprobs;
+  return logprobs_workspace_bytes(rows, vocab > 0 ? vocab : 1);
+}
+
+int aic_token_logprobs(const void* logits, int logits_dtype, int64_t row_stride, int vocab, const int64_t* row_index,
+                       const int32_t* token_ids, int rows, int num_logprobs, int32_t* out_token_ids, float* out_logprobs,
+                       int64_t* out_ranks, void* workspace, void* stream) {
+  return dispatch_logprobs(logits, logits_dtype, row_stride, vocab, row_index, token_ids, rows, num_logprobs,
+                           out_token_ids, out_logprobs, out_ranks, workspace, stream);
 }
 
 }  // extern "C"

@@ -225,6 +225,49 @@ def sample_tokens(logits: torch.Tensor, temperature: torch.Tensor, exp_noise: Op
     return out
 
 
+def token_logprobs(logits: torch.Tensor, num_logprobs: int, *, token_ids: Optional[torch.Tensor] = None,
+                   row_index: Optional[torch.Tensor] = None, check_token_ids: bool = True
+                   ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(token ids int32 [rows, 1+n], logprobs f32 [rows, 1+n], ranks int64 [rows]) as vLLM's Sampler.compute_logprobs +
+    gather_logprobs give them (aic_token_logprobs): column 0 is the selected token, columns 1..n the n = `num_logprobs`
+    largest entries of the row by (value descending, index ascending); logprobs are the f32 log-softmax of the raw row,
+    the rank counts the raw values >= the selected token's.  `logits` [T, V] is read in place in its own dtype;
+    `row_index` (int64 [rows]) names the rows (SpecDecodeMetadata.bonus_logits_indices) instead of a gathered copy, else
+    every row is served.  `token_ids` (int [rows]): the selected tokens; None: each row's arg-max (ties to the lowest
+    index).  Ids outside [0, V) raise; reading them back costs a host synchronisation, so the check is skipped while the
+    stream is being captured and with `check_token_ids=False` (a caller whose ids come from ops.sample_tokens): the
+    kernel then answers such a row with a NaN logprob and rank 0 and never indexes out of the row."""
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("logits must be [T, V] with contiguous rows")
+    if row_index is not None and (row_index.dtype != torch.int64 or row_index.dim() != 1):
+        raise ValueError("row_index must be int64 [rows]")
+    rows = int(row_index.numel()) if row_index is not None else int(logits.size(0))
+    V = int(logits.size(1))
+    n = int(num_logprobs)
+    cap = int(N.lib().aic_logprobs_max())
+    if not 0 <= n <= cap or n > V:
+        raise ValueError(f"num_logprobs must be in 0 .. {min(cap, V)} (got {n})")
+    tok = None if token_ids is None else token_ids.reshape(-1).to(torch.int32)
+    if tok is not None and tok.numel() != rows:
+        raise ValueError("token_ids: one token per row")
+    _need_cuda(logits, token_ids, row_index)
+    dev = logits.device
+    out_ids = torch.empty((rows, 1 + n), dtype=torch.int32, device=dev)
+    out_lp = torch.empty((rows, 1 + n), dtype=torch.float32, device=dev)
+    out_rank = torch.empty(rows, dtype=torch.int64, device=dev)
+    if rows == 0:
+        return out_ids, out_lp, out_rank
+    if tok is not None and check_token_ids and not torch.cuda.is_current_stream_capturing():
+        if bool(((tok < 0) | (tok >= V)).any()):
+            raise ValueError(f"token_ids outside [0, {V})")
+    dt = N.torch_dtype_code(logits.dtype)
+    ws = _workspace(N.lib().aic_logprobs_workspace_bytes(rows, V, dt, n), dev, purpose="accept")
+    N.check(N.lib().aic_token_logprobs(logits.data_ptr(), dt, int(logits.stride(0)), V, _ptr(row_index), _ptr(tok), rows, n,
+                                       out_ids.data_ptr(), out_lp.data_ptr(), out_rank.data_ptr(), ws.data_ptr(),
+                                       N.current_stream_ptr()))
+    return out_ids, out_lp, out_rank
+
+
 # ------------------------------------------------------------------------------------------------
 # A5 verify attention
 # ------------------------------------------------------------------------------------------------

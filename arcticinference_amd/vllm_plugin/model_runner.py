@@ -32,8 +32,8 @@ import torch
 
 from . import step_context
 from .runner_logic import (INDEXING_REFERENCE, KIND_TOP_K_TOP_P, MAX_SPEC_LEN, arctic_max_spec_tokens, hip_acceptance_kind,
-                           hip_sampler_ok, hip_sampler_switch, merge_proposals, min_suffix_score, proposal_end_index,
-                           proposal_indexing, rewrite_sampled, suffix_query, top_k_top_p_switch)
+                           hip_sampler_ok, hip_sampler_switch, logprobs_switch, merge_proposals, min_suffix_score,
+                           proposal_end_index, proposal_indexing, rewrite_sampled, suffix_query, top_k_top_p_switch)
 
 logger = logging.getLogger(__name__)
 
@@ -126,6 +126,21 @@ def hip_sample(logits: torch.Tensor, sm, row_index: Optional[torch.Tensor] = Non
         return ops.sample_tokens(logits, temperature, None, row_index=row_index)
     noise = draw_sampler_noise(rows, logits.shape[-1], sm.generators, logits.device)
     return ops.sample_tokens(logits, sm.temperature, noise, top_k=sm.top_k, top_p=sm.top_p, row_index=row_index)
+
+
+def hip_logprobs(logits: torch.Tensor, sm, tokens: Optional[torch.Tensor] = None,
+                 row_index: Optional[torch.Tensor] = None):
+    """vLLM's LogprobsTensors of one sampler call (Sampler.compute_logprobs + gather_logprobs) from the HIP kernel, or
+    None when the step reports no logprobs: those of `tokens` (the arg-max of each row when None) on `logits[row_index]`
+    (every row when None), read in place.  `tokens` come from the HIP sampler, so their range is not checked again (the
+    check would be a host synchronisation).  Field names recalled from vLLM 0.9.2 (v1/outputs.py)."""
+    if sm.max_num_logprobs is None:
+        return None
+    from vllm.v1.outputs import LogprobsTensors
+    from .. import ops
+    ids, lps, ranks = ops.token_logprobs(logits, int(sm.max_num_logprobs), token_ids=tokens, row_index=row_index,
+                                         check_token_ids=False)
+    return LogprobsTensors(logprob_token_ids=ids, logprobs=lps, selected_token_ranks=ranks)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -509,35 +524,52 @@ def build_model_runner_patch():
                 aic_rejection_random accepts;
               * with ARCTIC_INFERENCE_HIP_TOP_K_TOP_P=1 (read once per step), batches whose rows also carry top-k /
                 top-p take the same route through aic_rejection_random_topk_topp (the bonus tokens stay vLLM's sampler's).
-            Anything else (min-p, penalties, bias, min_tokens, masks, logprobs, and top-k / top-p with the switch off:
+            Anything else (min-p, penalties, bias, min_tokens, masks, and top-k / top-p with the switch off:
             runner_logic.hip_acceptance_kind) keeps vLLM's sampler + RejectionSampler.
             With ARCTIC_INFERENCE_HIP_SAMPLER=1 (read once per step; runner_logic.hip_sampler_ok) vLLM's sampler itself
             is replaced by aic_sample_topk_topp: steps without draft tokens are sampled whole, and in the random verify
             steps above the bonus tokens are sampled from the bonus rows of `logits` in place (no gather, no f32 copy),
-            before the uniforms and the recovery noise as in vLLM, and stay on the device for the acceptance call."""
+            before the uniforms and the recovery noise as in vLLM, and stay on the device for the acceptance call.
+            A step in which a request asks for logprobs (`max_num_logprobs` not None) is vLLM's throughout unless
+            ARCTIC_INFERENCE_HIP_LOGPROBS=1 (read once per step) and `max_num_logprobs` <= aic_logprobs_max().  Then the
+            routes above stay on, and the step's logprobs_tensors are, as in the reference (:383-399, :438-440), those
+            of the one sampler call — all rows of a draft-free step, the bonus rows and bonus tokens of a verify step,
+            emitted or not; the acceptance never touches them:
+              * tokens drawn by the HIP sampler: ops.token_logprobs (aic_token_logprobs) on the same rows in place,
+                issued before the uniforms and the recovery noise are drawn (it consumes no generator);
+              * the all-greedy verify launch: still ONE acceptance launch, and ops.token_logprobs on the bonus rows
+                without token ids (each row's arg-max, the token that launch takes);
+              * bonus tokens drawn by vLLM's sampler: its logprobs_tensors pass through untouched."""
             sm = sampling_metadata
-            hip_sampler = (hip_sampler_switch() and logits is not None and logits.is_cuda and hip_sampler_ok(sm))
+            lp = logprobs_switch()
+            hip_sampler = (hip_sampler_switch() and logits is not None and logits.is_cuda and hip_sampler_ok(sm, lp))
             if spec_decode_metadata is None:
                 if hip_sampler:
                     from vllm.v1.outputs import SamplerOutput
-                    return SamplerOutput(sampled_token_ids=hip_sample(logits, sm).view(-1, 1), logprobs_tensors=None)
+                    tokens = hip_sample(logits, sm)
+                    return SamplerOutput(sampled_token_ids=tokens.view(-1, 1),
+                                         logprobs_tensors=hip_logprobs(logits, sm, tokens))
                 return self.sampler(logits=logits, sampling_metadata=sampling_metadata)
             assert logits is not None
             md = spec_decode_metadata
-            kind = hip_acceptance_kind(sm, top_k_top_p_switch()) if logits.is_cuda else None
+            kind = hip_acceptance_kind(sm, top_k_top_p_switch(), lp) if logits.is_cuda else None
             if kind == "greedy":
                 from vllm.v1.outputs import SamplerOutput
                 max_spec = max(int(max(md.num_draft_tokens)), 1)
+                bonus_rows = md.bonus_logits_indices.to(torch.int64)
                 rej = ops.rejection_sample(logits, md.draft_token_ids, md.cu_num_draft_tokens, None, max_spec,
                                            target_row_index=md.target_logits_indices.to(torch.int64),
-                                           bonus_row_index=md.bonus_logits_indices.to(torch.int64))
+                                           bonus_row_index=bonus_rows)
                 self._arctic_rej = rej
                 self._arctic_maybe_draft_early(rej, sample_hidden_states, md.num_draft_tokens)
-                return SamplerOutput(sampled_token_ids=rej.output_token_ids, logprobs_tensors=None)
+                return SamplerOutput(sampled_token_ids=rej.output_token_ids,
+                                     logprobs_tensors=hip_logprobs(logits, sm, None, bonus_rows))
             if hip_sampler and kind in ("random", KIND_TOP_K_TOP_P):
                 from vllm.v1.outputs import SamplerOutput
-                bonus = hip_sample(logits, sm, md.bonus_logits_indices.to(torch.int64))
-                out = SamplerOutput(sampled_token_ids=bonus.view(-1, 1), logprobs_tensors=None)
+                bonus_rows = md.bonus_logits_indices.to(torch.int64)
+                bonus = hip_sample(logits, sm, bonus_rows)
+                out = SamplerOutput(sampled_token_ids=bonus.view(-1, 1),
+                                    logprobs_tensors=hip_logprobs(logits, sm, bonus, bonus_rows))
             else:
                 # indexing with a tensor copies: in-place edits of the sampler do not reach `logits`
                 bonus_logits = logits[md.bonus_logits_indices]

@@ -112,15 +112,39 @@ def top_k_top_p_switch() -> bool:
     return os.environ.get(TOP_K_TOP_P_ENV, "0").strip().lower() in ("1", "true", "yes", "on")
 
 
-def hip_acceptance_kind(sm, top_k_top_p: bool = False) -> Optional[str]:
+LOGPROBS_ENV = "ARCTIC_INFERENCE_HIP_LOGPROBS"   # 1: steps with logprobs requests keep the HIP sampler / acceptance (default off)
+
+
+def logprobs_switch() -> bool:
+    return os.environ.get(LOGPROBS_ENV, "0").strip().lower() in ("1", "true", "yes", "on")
+
+
+def logprobs_cap() -> int:
+    """The largest `max_num_logprobs` aic_token_logprobs serves (aic_logprobs_max)."""
+    from .. import _native
+    return int(_native.lib().aic_logprobs_max())
+
+
+def _logprobs_excluded(sm, logprobs: bool) -> bool:
+    n = getattr(sm, "max_num_logprobs", None)
+    if n is None:
+        return False
+    return not (logprobs and 0 <= int(n) <= logprobs_cap())
+
+
+def hip_acceptance_kind(sm, top_k_top_p: bool = False, logprobs: bool = False) -> Optional[str]:
     """Which acceptance kernel serves a verify step with this vLLM SamplingMetadata: "greedy" (aic_rejection_greedy),
     "random" (aic_rejection_random: temperature-only rows, greedy rows mixed in), "random_topk_topp"
     (aic_rejection_random_topk_topp: rows with top-k / top-p as well; only when `top_k_top_p`, the TOP_K_TOP_P_ENV
-    switch) or None (vLLM's sampler + RejectionSampler: min-p, penalties, logit bias, min_tokens, bad words,
-    allowed-token masks and logprobs live there, and top-k / top-p with the switch off).  Read field by field the way vLLM 0.9.2's InputBatch fills it: `logit_bias` is a list with one
+    switch) or None (vLLM's sampler + RejectionSampler: min-p, penalties, logit bias, min_tokens, bad words and
+    allowed-token masks live there, and top-k / top-p with the switch off).  A step that reports logprobs
+    (`max_num_logprobs` not None) is excluded too unless `logprobs` (the LOGPROBS_ENV switch) is set and
+    `max_num_logprobs` is within 0 .. aic_logprobs_max(): the acceptance never touches logprobs, they are those of the
+    bonus rows' sampler call, which the caller serves (ops.token_logprobs, or vLLM's sampler where it still draws the
+    bonus tokens).  Read field by field the way vLLM 0.9.2's InputBatch fills it: `logit_bias` is a list with one
     entry per request (None where unused) and is therefore never empty; `min_tokens` / `bad_words_token_ids` are dicts;
     tensors are None when no request uses them."""
-    if getattr(sm, "max_num_logprobs", None) is not None or not getattr(sm, "no_penalties", True):
+    if _logprobs_excluded(sm, logprobs) or not getattr(sm, "no_penalties", True):
         return None
     if getattr(sm, "allowed_token_ids_mask", None) is not None or getattr(sm, "bad_words_token_ids", None):
         return None
@@ -144,12 +168,14 @@ def hip_sampler_switch() -> bool:
     return os.environ.get(HIP_SAMPLER_ENV, "0").strip().lower() in ("1", "true", "yes", "on")
 
 
-def hip_sampler_ok(sm) -> bool:
+def hip_sampler_ok(sm, logprobs: bool = False) -> bool:
     """Whether ops.sample_tokens (aic_sample_topk_topp: temperature, top-k, top-p; greedy rows mixed in or all-greedy)
-    can stand in for vLLM's Sampler on this SamplingMetadata.  The exclusions are those of hip_acceptance_kind: logprobs,
-    penalties, allowed-token masks, bad words, logit bias, min_tokens and min-p keep vLLM's sampler.  `top_k` / `top_p`
-    are served as tensors and as None."""
-    if getattr(sm, "max_num_logprobs", None) is not None or not getattr(sm, "no_penalties", True):
+    can stand in for vLLM's Sampler on this SamplingMetadata.  The exclusions are those of hip_acceptance_kind:
+    penalties, allowed-token masks, bad words, logit bias, min_tokens and min-p keep vLLM's sampler, and so does a step
+    that reports logprobs unless `logprobs` (the LOGPROBS_ENV switch) is set and `max_num_logprobs` is within
+    0 .. aic_logprobs_max(): the caller then reports them with ops.token_logprobs.  `top_k` / `top_p` are served as
+    tensors and as None."""
+    if _logprobs_excluded(sm, logprobs) or not getattr(sm, "no_penalties", True):
         return False
     if getattr(sm, "allowed_token_ids_mask", None) is not None or getattr(sm, "bad_words_token_ids", None):
         return False

@@ -325,6 +325,36 @@ size_t aic_sample_workspace_bytes(int rows, int vocab, int logits_dtype);
 int aic_sample_topk_topp(const void* logits, int logits_dtype, int64_t row_stride, int vocab, const int64_t* row_index,
                          const float* temperature, const float* exp_noise, const int32_t* top_k, const float* top_p,
                          int rows, int32_t* out_token_ids, void* workspace, void* stream);
+/* Token logprobs — vLLM 0.9.2's Sampler.compute_logprobs (log_softmax(dtype=float32) of the RAW logits) and
+ * gather_logprobs (vllm/v1/sample/sampler.py; both recalled, parity unpinned like the rest of A6), for the steps whose
+ * tokens aic_sample_topk_topp or the folded greedy acceptance draws.  Row r of the call is
+ * logits[row_index ? row_index[r] : r] (row stride in elements; bf16 / fp16 / f32 rows are read in place: no f32 copy
+ * and no gathered copy of a row is made).
+ *   token      token_ids[r] (int32 [rows]); token_ids == NULL: the arg-max of the raw row in f32, ties to the lowest
+ *              index (what the all-greedy verify launch emits for a bonus row).
+ *   logprob    logprob(v) = (x_v - m) - log(s), m the row maximum, s = sum_v exp(x_v - m) accumulated in 2^-40 fixed
+ *              point (integer adds: order-free); all arithmetic in f32, no float atomics.  -inf logits (a grammar bitmask
+ *              writes them before sampling) add 0 to s and have logprob -inf.
+ *   columns    out_token_ids / out_logprobs are [rows][1 + n], n = num_logprobs in 0 .. aic_logprobs_max() (32).
+ *              Column 0: the selected token and its logprob.  Columns 1 .. n: the n largest entries of the row by
+ *              descending value; equal values by ascending index, and the same rule decides which of several tied values
+ *              make the cut.  torch.topk leaves that order unspecified: the rule refines vLLM's behaviour, it does not
+ *              deviate from it.
+ *   rank       out_ranks[r] (int64) = #{v : x_v >= x_token} on the RAW values: 1 for the arg-max, tokens tied with the
+ *              selected one count.  vLLM counts on the f32 logprobs; the two counts can differ only for f32 logits whose
+ *              distinct values merge after the subtraction of m and log s.
+ * Returns an error before any launch for num_logprobs outside 0 .. aic_logprobs_max(), num_logprobs > vocab or an
+ * unknown dtype.  token_ids live in device memory: the call cannot read them without a host synchronisation, so it does
+ * not.  The kernels never index a row with an id outside [0, vocab): such a row gets a NaN logprob and rank 0 in column
+ * 0 (its other columns are right), and callers that can afford the synchronisation check the ids first
+ * (ops.token_logprobs does, outside graph capture).  NaN logits are outside the contract.
+ * Deterministic, capturable (no host sync, no allocation); rows == 0 is a no-op.
+ * workspace: >= aic_logprobs_workspace_bytes(rows, vocab, logits_dtype, num_logprobs) bytes of HBM. */
+int aic_logprobs_max(void);
+size_t aic_logprobs_workspace_bytes(int rows, int vocab, int logits_dtype, int num_logprobs);
+int aic_token_logprobs(const void* logits, int logits_dtype, int64_t row_stride, int vocab, const int64_t* row_index,
+                       const int32_t* token_ids, int rows, int num_logprobs, int32_t* out_token_ids, float* out_logprobs,
+                       int64_t* out_ranks, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A7-A11  Arctic LSTM speculator (sum_lstm) — replaces ArcticLSTMSpeculator.generate_proposals /

@@ -637,8 +637,52 @@ def sample(B=64, V=128256, top_k=None, top_p=None, indexed=False, reps=3):
           f"x{min(ref) / max(hip):5.1f} (fastest torch / slowest hip)   same tokens: {same}", flush=True)
 
 
+def _torch_logprobs(logits, idx, tokens, n):
+    """vLLM 0.9.2's Sampler.compute_logprobs + gather_logprobs on the rows `idx` of `logits` (recalled)."""
+    x = logits if idx is None else logits[idx]
+    lp = x.log_softmax(dim=-1, dtype=torch.float32)
+    tok = tokens.long().unsqueeze(-1)
+    tlp = lp.gather(-1, tok)
+    ranks = (lp >= tlp).sum(-1)
+    if n == 0:
+        return tok.to(torch.int32), tlp, ranks
+    tv, ti = torch.topk(lp, n, dim=-1)
+    return torch.cat((tok, ti), dim=1).to(torch.int32), torch.cat((tlp, tv), dim=1), ranks
+
+
+def logprobs(B=64, V=128256, n=20, indexed=False, reps=3):
+    """aic_token_logprobs (ops.token_logprobs) against the torch restatement of vLLM's two functions: same GPU, same
+    inputs, the two timed alternately `reps` times.  `indexed`: the rows are read through row_index out of a [256, V]
+    matrix (the bonus rows of a verify step) instead of from a gathered [B, V] one."""
+    g = torch.Generator(device=dev).manual_seed(0)
+    T = 256 if indexed else B
+    logits = (torch.randn(T, V, device=dev, generator=g) * 3).to(torch.bfloat16)
+    idx = (torch.arange(B, device=dev) * (T // B) + (T // B - 1)).to(torch.int64) if indexed else None
+    tokens = torch.randint(0, V, (B,), device=dev, generator=g).to(torch.int32)
+    hip_fn = lambda: ops.token_logprobs(logits, n, token_ids=tokens, row_index=idx, check_token_ids=False)
+    ref_fn = lambda: _torch_logprobs(logits, idx, tokens, n)
+    hip, ref = [], []
+    for _ in range(reps):
+        hip.append(timeit(hip_fn))
+        ref.append(timeit(ref_fn))
+    a, b = hip_fn(), ref_fn()
+    # random bf16 rows tie inside their top n: the ids of tied entries are torch.topk's choice, the values are not
+    same = (torch.equal(a[0][:, 0], b[0][:, 0]) and torch.equal(a[2], b[2])
+            and bool(((a[1] - b[1]).abs() <= 1e-5 + 2.0 ** -20 * b[1].abs()).all()))
+    passes = 2 + (1 if n else 0)          # bf16 keys: first, digit 1 (+ sum and rank), gather
+    fmt = lambda v: " / ".join(f"{x:7.1f}" for x in v)
+    print(f"logprobs B={B} V={V} n={n:2d} {'row_index' if indexed else 'gathered '}: hip {fmt(hip)} us "
+          f"({passes} passes, {passes * B * V * 2 / 1e9 / min(hip) * 1e6 / 1e3:5.2f} TB/s effective)   torch {fmt(ref)} us   "
+          f"x{min(ref) / max(hip):5.1f} (fastest torch / slowest hip)   same values and ranks: {same}", flush=True)
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["attn", "lstm", "rej"]
+    if "logprobs" in what:
+        for V in (128256, 201088):
+            for indexed in (False, True):
+                for n in (0, 1, 20):
+                    logprobs(V=V, n=n, indexed=indexed)
     if "sample" in what:
         for V in (128256, 201088):
             for indexed in (False, True):
