@@ -136,6 +136,11 @@ _SIGNATURES = {
     "aic_logprobs_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "aic_token_logprobs": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_void_p]),
+    "aic_logits_edit_segment": (c_int, []),
+    "aic_logits_edit_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "aic_logits_edit": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "aic_lstm_create": (c_int, [POINTER(LstmConfig), POINTER(LstmWeights), POINTER(c_void_p)]),
     "aic_mlp_create": (c_int, [POINTER(LstmConfig), POINTER(MlpWeights), POINTER(c_void_p)]),
     "aic_mlp_create_stacked": (c_int, [POINTER(LstmConfig), POINTER(MlpWeights), POINTER(MlpStack), POINTER(c_void_p)]),

@@ -268,6 +268,79 @@ def token_logprobs(logits: torch.Tensor, num_logprobs: int, *, token_ids: Option
     return out_ids, out_lp, out_rank
 
 
+def _csr(name: str, lists, rows: int, n_parts: int):
+    """Checks one CSR edit input of edit_logits: (offsets int32 [rows + 1], tokens int32 [n][, values f32 [n]])."""
+    if lists is None:
+        return (None,) * n_parts + (0,)
+    if len(lists) != n_parts:
+        raise ValueError(f"{name}: {n_parts} tensors (offsets, tokens{', values' if n_parts == 3 else ''})")
+    off, tok = lists[0], lists[1]
+    if off.dtype != torch.int32 or off.dim() != 1 or off.numel() != rows + 1 or not off.is_contiguous():
+        raise ValueError(f"{name}: offsets must be contiguous int32 [rows + 1]")
+    if tok.dtype != torch.int32 or tok.dim() != 1 or not tok.is_contiguous():
+        raise ValueError(f"{name}: tokens must be contiguous int32 [n]")
+    if n_parts == 3:
+        val = lists[2]
+        if val.dtype != torch.float32 or val.dim() != 1 or val.numel() != tok.numel() or not val.is_contiguous():
+            raise ValueError(f"{name}: values must be contiguous float32, one per token")
+    _need_cuda(*lists)
+    return tuple(lists) + (int(tok.numel()),)
+
+
+def logits_edit_segment() -> int:
+    """The tokens one workgroup of aic_logits_edit serves (tests place histories on both sides of a boundary)."""
+    return int(N.lib().aic_logits_edit_segment())
+
+
+def edit_logits(logits: torch.Tensor, *, allowed_mask: Optional[torch.Tensor] = None, ban=None, bias=None, prompt=None,
+                output=None, repetition: Optional[torch.Tensor] = None, frequency: Optional[torch.Tensor] = None,
+                presence: Optional[torch.Tensor] = None, min_p: Optional[torch.Tensor] = None,
+                temperature: Optional[torch.Tensor] = None, row_index: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """f32 [rows, V]: the rows of `logits` as vLLM's Sampler leaves them before it samples (aic_logits_edit): allowed
+    mask, bans, bias, repetition / frequency / presence penalties, then min-p on the rows with temperature > 0 and
+    min_p > 0.  `logits` [T, V] (bf16 / fp16 / f32) is only read, in place; `row_index` (int64 [rows]) names the rows
+    (SpecDecodeMetadata.bonus_logits_indices), else every row is edited.  Every edit input may be None:
+    `allowed_mask` bool / uint8 [rows, V], non-zero = not allowed; `ban` = (offsets, tokens), `bias` = (offsets, tokens,
+    values), `prompt` / `output` = (offsets, tokens): int32 CSR, offsets [rows + 1], values f32; token ids outside
+    [0, V) are ignored; `repetition` / `frequency` / `presence` / `min_p` / `temperature` f32 [rows].  Wrong dtypes or
+    shapes, and min_p without temperature, raise before anything is launched."""
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("logits must be [T, V] with contiguous rows")
+    if logits.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise ValueError(f"logits must be bf16, fp16 or f32 (got {logits.dtype})")
+    if row_index is not None and (row_index.dtype != torch.int64 or row_index.dim() != 1):
+        raise ValueError("row_index must be int64 [rows]")
+    rows = int(row_index.numel()) if row_index is not None else int(logits.size(0))
+    V = int(logits.size(1))
+    if allowed_mask is not None and (allowed_mask.dtype not in (torch.bool, torch.uint8) or
+                                     tuple(allowed_mask.shape) != (rows, V) or not allowed_mask.is_contiguous()):
+        raise ValueError("allowed_mask must be contiguous bool / uint8 [rows, V]")
+    for name, t in (("repetition", repetition), ("frequency", frequency), ("presence", presence), ("min_p", min_p),
+                    ("temperature", temperature)):
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 1 or t.numel() != rows or not t.is_contiguous()):
+            raise ValueError(f"{name} must be contiguous float32 [rows]")
+    if min_p is not None and temperature is None:
+        raise ValueError("min_p needs the rows' temperature")
+    ban_off, ban_tok, n_ban = _csr("ban", ban, rows, 2)
+    bias_off, bias_tok, bias_val, n_bias = _csr("bias", bias, rows, 3)
+    pr_off, pr_tok, n_pr = _csr("prompt", prompt, rows, 2)
+    ou_off, ou_tok, n_ou = _csr("output", output, rows, 2)
+    _need_cuda(logits, allowed_mask, repetition, frequency, presence, min_p, temperature, row_index)
+    dev = logits.device
+    out = torch.empty((rows, V), dtype=torch.float32, device=dev)
+    if rows == 0:
+        return out
+    ws = None
+    if min_p is not None:
+        ws = _workspace(N.lib().aic_logits_edit_workspace_bytes(rows, V), dev, purpose="accept")
+    N.check(N.lib().aic_logits_edit(
+        logits.data_ptr(), N.torch_dtype_code(logits.dtype), int(logits.stride(0)), V, _ptr(row_index), rows,
+        _ptr(allowed_mask), _ptr(ban_off), _ptr(ban_tok), n_ban, _ptr(bias_off), _ptr(bias_tok), _ptr(bias_val), n_bias,
+        _ptr(pr_off), _ptr(pr_tok), n_pr, _ptr(ou_off), _ptr(ou_tok), n_ou, _ptr(repetition), _ptr(frequency),
+        _ptr(presence), _ptr(min_p), _ptr(temperature), out.data_ptr(), _ptr(ws), N.current_stream_ptr()))
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # A5 verify attention
 # ------------------------------------------------------------------------------------------------

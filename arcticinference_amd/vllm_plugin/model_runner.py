@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from . import step_context
+from .logits_edits import has_edits, logits_edits_switch, pack_edits
 from .runner_logic import (INDEXING_REFERENCE, KIND_TOP_K_TOP_P, MAX_SPEC_LEN, arctic_max_spec_tokens, hip_acceptance_kind,
                            hip_sampler_ok, hip_sampler_switch, logprobs_switch, merge_proposals, min_suffix_score,
                            proposal_end_index, proposal_indexing, rewrite_sampled, suffix_query, top_k_top_p_switch)
@@ -126,6 +127,15 @@ def hip_sample(logits: torch.Tensor, sm, row_index: Optional[torch.Tensor] = Non
         return ops.sample_tokens(logits, temperature, None, row_index=row_index)
     noise = draw_sampler_noise(rows, logits.shape[-1], sm.generators, logits.device)
     return ops.sample_tokens(logits, sm.temperature, noise, top_k=sm.top_k, top_p=sm.top_p, row_index=row_index)
+
+
+def hip_edit(logits: torch.Tensor, sm, row_index: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The rows vLLM's Sampler would sample after its logits edits (penalties, bias, bans, masks, min-p), as f32
+    [rows, V] from the HIP kernel: `logits[row_index]` (every row when None) is only read — logprobs stay those of the
+    raw rows.  Row i is request i of the SamplingMetadata.  Consumes no generator."""
+    from .. import ops
+    rows = int(row_index.numel()) if row_index is not None else int(logits.shape[0])
+    return ops.edit_logits(logits, row_index=row_index, **pack_edits(sm, rows, logits.device))
 
 
 def hip_logprobs(logits: torch.Tensor, sm, tokens: Optional[torch.Tensor] = None,
@@ -539,21 +549,35 @@ def build_model_runner_patch():
                 issued before the uniforms and the recovery noise are drawn (it consumes no generator);
               * the all-greedy verify launch: still ONE acceptance launch, and ops.token_logprobs on the bonus rows
                 without token ids (each row's arg-max, the token that launch takes);
-              * bonus tokens drawn by vLLM's sampler: its logprobs_tensors pass through untouched."""
+              * bonus tokens drawn by vLLM's sampler: its logprobs_tensors pass through untouched.
+            With ARCTIC_INFERENCE_HIP_LOGITS_EDITS=1 (read once per step) a step in which a request edits its logits
+            (logits_edits.has_edits: penalties, min-p, bias, min_tokens, bad words, allowed-token masks) keeps the routes
+            above; a step without such a request is not touched by the switch and makes no extra launch.  The edits act
+            on the one sampler call only — vLLM's rejection sampler never reads them — so:
+              * the acceptance reads the RAW target rows as before, and always takes the bonus tokens as an argument
+                (the all-greedy launch too: its own bonus arg-max would read the raw rows);
+              * with the sampler switch on, the sampler's rows (every row of a draft-free step, the bonus rows of a verify
+                step) go through ops.edit_logits into an f32 copy, which hip_sample reads; `logits` is never written,
+                and the logprobs are those of the raw rows, as in vLLM;
+              * with the sampler switch off, vLLM's sampler edits its own gathered copy of the bonus rows as today.
+            The edit draws nothing, so the generator order (sampler noise, uniforms, recovery noise) is unchanged."""
             sm = sampling_metadata
             lp = logprobs_switch()
-            hip_sampler = (hip_sampler_switch() and logits is not None and logits.is_cuda and hip_sampler_ok(sm, lp))
+            le = logits_edits_switch()
+            on_gpu = logits is not None and logits.is_cuda
+            hip_sampler = hip_sampler_switch() and on_gpu and hip_sampler_ok(sm, lp, logits_edits=le)
+            edits = le and on_gpu and has_edits(sm)
             if spec_decode_metadata is None:
                 if hip_sampler:
                     from vllm.v1.outputs import SamplerOutput
-                    tokens = hip_sample(logits, sm)
+                    tokens = hip_sample(hip_edit(logits, sm) if edits else logits, sm)
                     return SamplerOutput(sampled_token_ids=tokens.view(-1, 1),
                                          logprobs_tensors=hip_logprobs(logits, sm, tokens))
                 return self.sampler(logits=logits, sampling_metadata=sampling_metadata)
             assert logits is not None
             md = spec_decode_metadata
-            kind = hip_acceptance_kind(sm, top_k_top_p_switch(), lp) if logits.is_cuda else None
-            if kind == "greedy":
+            kind = hip_acceptance_kind(sm, top_k_top_p_switch(), lp, logits_edits=le) if logits.is_cuda else None
+            if kind == "greedy" and not edits:
                 from vllm.v1.outputs import SamplerOutput
                 max_spec = max(int(max(md.num_draft_tokens)), 1)
                 bonus_rows = md.bonus_logits_indices.to(torch.int64)
@@ -564,16 +588,28 @@ def build_model_runner_patch():
                 self._arctic_maybe_draft_early(rej, sample_hidden_states, md.num_draft_tokens)
                 return SamplerOutput(sampled_token_ids=rej.output_token_ids,
                                      logprobs_tensors=hip_logprobs(logits, sm, None, bonus_rows))
-            if hip_sampler and kind in ("random", KIND_TOP_K_TOP_P):
+            if hip_sampler and kind is not None:
                 from vllm.v1.outputs import SamplerOutput
                 bonus_rows = md.bonus_logits_indices.to(torch.int64)
-                bonus = hip_sample(logits, sm, bonus_rows)
+                if edits:
+                    bonus = hip_sample(hip_edit(logits, sm, bonus_rows), sm)
+                else:
+                    bonus = hip_sample(logits, sm, bonus_rows)
                 out = SamplerOutput(sampled_token_ids=bonus.view(-1, 1),
                                     logprobs_tensors=hip_logprobs(logits, sm, bonus, bonus_rows))
             else:
                 # indexing with a tensor copies: in-place edits of the sampler do not reach `logits`
                 bonus_logits = logits[md.bonus_logits_indices]
                 out = self.sampler(logits=bonus_logits, sampling_metadata=sampling_metadata)
+            if kind == "greedy":
+                # a step with edits: the launch's own bonus arg-max would read the raw rows, so the bonus tokens are passed
+                max_spec = max(int(max(md.num_draft_tokens)), 1)
+                rej = ops.rejection_sample(logits, md.draft_token_ids, md.cu_num_draft_tokens, out.sampled_token_ids,
+                                           max_spec, target_row_index=md.target_logits_indices.to(torch.int64))
+                self._arctic_rej = rej
+                self._arctic_maybe_draft_early(rej, sample_hidden_states, md.num_draft_tokens)
+                out.sampled_token_ids = rej.output_token_ids
+                return out
             if kind in ("random", KIND_TOP_K_TOP_P):
                 filters = dict(top_k=sm.top_k, top_p=sm.top_p) if kind == KIND_TOP_K_TOP_P else {}
                 n_draft = md.num_draft_tokens

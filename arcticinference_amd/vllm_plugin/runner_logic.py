@@ -6,6 +6,8 @@ from __future__ import annotations
 import os
 from typing import List, Optional, Sequence, Tuple
 
+from .logits_edits import LOGITS_EDITS_ENV, has_edits, logits_edits_switch  # noqa: F401  (the switch lives with the packing)
+
 MAX_SPEC_LEN = 32  # vllm.v1.sample.rejection_sampler.MAX_SPEC_LEN
 
 # ---------------------------------------------------------------------------------------------------
@@ -132,7 +134,7 @@ def _logprobs_excluded(sm, logprobs: bool) -> bool:
     return not (logprobs and 0 <= int(n) <= logprobs_cap())
 
 
-def hip_acceptance_kind(sm, top_k_top_p: bool = False, logprobs: bool = False) -> Optional[str]:
+def hip_acceptance_kind(sm, top_k_top_p: bool = False, logprobs: bool = False, logits_edits: bool = False) -> Optional[str]:
     """Which acceptance kernel serves a verify step with this vLLM SamplingMetadata: "greedy" (aic_rejection_greedy),
     "random" (aic_rejection_random: temperature-only rows, greedy rows mixed in), "random_topk_topp"
     (aic_rejection_random_topk_topp: rows with top-k / top-p as well; only when `top_k_top_p`, the TOP_K_TOP_P_ENV
@@ -143,14 +145,14 @@ def hip_acceptance_kind(sm, top_k_top_p: bool = False, logprobs: bool = False) -
     bonus rows' sampler call, which the caller serves (ops.token_logprobs, or vLLM's sampler where it still draws the
     bonus tokens).  Read field by field the way vLLM 0.9.2's InputBatch fills it: `logit_bias` is a list with one
     entry per request (None where unused) and is therefore never empty; `min_tokens` / `bad_words_token_ids` are dicts;
-    tensors are None when no request uses them."""
-    if _logprobs_excluded(sm, logprobs) or not getattr(sm, "no_penalties", True):
-        return None
-    if getattr(sm, "allowed_token_ids_mask", None) is not None or getattr(sm, "bad_words_token_ids", None):
-        return None
-    if any(b is not None and len(b) > 0 for b in (getattr(sm, "logit_bias", None) or ())):
-        return None
-    if getattr(sm, "min_tokens", None) or getattr(sm, "min_p", None) is not None:
+    tensors are None when no request uses them.
+    With `logits_edits` (the LOGITS_EDITS_ENV switch) the edit fields — min-p, penalties, logit bias, min_tokens, bad
+    words, allowed-token masks: logits_edits.has_edits — no longer exclude a step, and the result is that of the same
+    metadata without them: vLLM's rejection sampler never reads them (its probabilities come from temperature and
+    top-k / top-p alone), they act on the bonus rows' sampler call only.  The caller then draws the bonus tokens from
+    the edited rows (ops.edit_logits, or vLLM's sampler on its own copy) and hands them to the acceptance as
+    `bonus_token_ids`, the all-greedy launch included: its own bonus arg-max reads the raw rows."""
+    if _logprobs_excluded(sm, logprobs) or (not logits_edits and has_edits(sm)):
         return None
     if getattr(sm, "all_greedy", False):
         return "greedy"
@@ -168,20 +170,16 @@ def hip_sampler_switch() -> bool:
     return os.environ.get(HIP_SAMPLER_ENV, "0").strip().lower() in ("1", "true", "yes", "on")
 
 
-def hip_sampler_ok(sm, logprobs: bool = False) -> bool:
+def hip_sampler_ok(sm, logprobs: bool = False, logits_edits: bool = False) -> bool:
     """Whether ops.sample_tokens (aic_sample_topk_topp: temperature, top-k, top-p; greedy rows mixed in or all-greedy)
     can stand in for vLLM's Sampler on this SamplingMetadata.  The exclusions are those of hip_acceptance_kind:
     penalties, allowed-token masks, bad words, logit bias, min_tokens and min-p keep vLLM's sampler, and so does a step
     that reports logprobs unless `logprobs` (the LOGPROBS_ENV switch) is set and `max_num_logprobs` is within
     0 .. aic_logprobs_max(): the caller then reports them with ops.token_logprobs.  `top_k` / `top_p` are served as
-    tensors and as None."""
-    if _logprobs_excluded(sm, logprobs) or not getattr(sm, "no_penalties", True):
-        return False
-    if getattr(sm, "allowed_token_ids_mask", None) is not None or getattr(sm, "bad_words_token_ids", None):
-        return False
-    if any(b is not None and len(b) > 0 for b in (getattr(sm, "logit_bias", None) or ())):
-        return False
-    if getattr(sm, "min_tokens", None) or getattr(sm, "min_p", None) is not None:
+    tensors and as None.  With `logits_edits` (the LOGITS_EDITS_ENV switch) the edit fields no longer exclude a step:
+    the caller samples the rows ops.edit_logits returns (logits_edits.pack_edits), and reports logprobs of the RAW
+    rows as vLLM does."""
+    if _logprobs_excluded(sm, logprobs) or (not logits_edits and has_edits(sm)):
         return False
     return bool(getattr(sm, "all_greedy", False)) or getattr(sm, "temperature", None) is not None
 

@@ -355,6 +355,42 @@ size_t aic_logprobs_workspace_bytes(int rows, int vocab, int logits_dtype, int n
 int aic_token_logprobs(const void* logits, int logits_dtype, int64_t row_stride, int vocab, const int64_t* row_index,
                        const int32_t* token_ids, int rows, int num_logprobs, int32_t* out_token_ids, float* out_logprobs,
                        int64_t* out_ranks, void* workspace, void* stream);
+/* Logits edits — what vLLM 0.9.2's Sampler.forward does to a row before it samples it (vllm/v1/sample/sampler.py:
+ * apply_allowed_token_ids, apply_bad_words, apply_logits_bias, apply_penalties, apply_min_p; vllm/v1/sample/ops/penalties.py:
+ * apply_min_token_penalties, apply_all_penalties; vllm/v1/sample/ops/bad_words.py; vllm/model_executor/layers/utils.py:
+ * apply_penalties; all recalled, parity unpinned like the rest of A6), for the one Sampler call of a step: every row of a
+ * draft-free step, the bonus rows of a verify step.  Row r of the call is logits[row_index ? row_index[r] : r] (row
+ * stride in elements; bf16 / fp16 / f32, the dtype codes of aic_sample_topk_topp).  The raw rows are only read — vLLM
+ * reports the logprobs of the raw logits — and `out` is contiguous f32 [rows][vocab].  Every edit input may be NULL
+ * (nobody uses it); the lists are int32 CSR: row r owns entries offsets[r] .. offsets[r + 1] of `num_*` in all (offsets
+ * are held inside 0 .. num_*, so no list is read out of bounds), and a token id outside [0, vocab) is ignored (vLLM
+ * pads prompts with `vocab`).  Per token, each step rounded once in f32:
+ *   1  x = f32(raw)
+ *   2  allowed_mask uint8 / bool [rows][vocab]: non-zero -> x = -inf          (masked_fill_ of allowed_token_ids_mask)
+ *   3  ban_offsets / ban_tokens: x = -inf                                     (bad words; min_tokens stop ids)
+ *   4  bias_offsets / bias_tokens / bias_values f32: x += bias                (a token listed twice gets both, in order)
+ *   5  seen = token in prompt_tokens or output_tokens of the row; p = seen ? repetition[r] : 1;
+ *      x *= (x > 0 ? 1 / p : p), 1 / p an IEEE division
+ *   6  x -= frequency[r] * count, count = occurrences in output_tokens (the product rounded, then the difference)
+ *   7  x -= presence[r] * (count > 0)
+ *   steps 5 - 7 run when any of repetition / frequency / presence is given; a missing one is 1 / 0 / 0.  -inf stays -inf.
+ *   min-p   rows with temperature[r] > 0 and min_p[r] > 0, in a second launch over the f32 rows: v stays iff
+ *           (x_v - m) / T >= ln(min_p), m the edited row's maximum; everything else becomes -inf.  The same set as
+ *           vLLM's probs < min_p * max_prob on the softmax of x / T up to rounding at the threshold (not bit-pinned).
+ *           Other rows are not touched by it: a greedy row is the arg-max of its edited row.
+ * Returns an error before any launch for min_p without temperature or workspace, offsets without their tokens, or an
+ * unknown dtype.  Integer LDS atomics only: deterministic; capturable (no host sync, no allocation); rows == 0 is a
+ * no-op.  aic_logits_edit_segment(): the tokens one workgroup serves (its LDS count array).
+ * workspace: >= aic_logits_edit_workspace_bytes(rows, vocab) bytes of HBM, read and written only with min_p. */
+int aic_logits_edit_segment(void);
+size_t aic_logits_edit_workspace_bytes(int rows, int vocab);
+int aic_logits_edit(const void* logits, int logits_dtype, int64_t row_stride, int vocab, const int64_t* row_index, int rows,
+                    const uint8_t* allowed_mask, const int32_t* ban_offsets, const int32_t* ban_tokens, int num_ban,
+                    const int32_t* bias_offsets, const int32_t* bias_tokens, const float* bias_values, int num_bias,
+                    const int32_t* prompt_offsets, const int32_t* prompt_tokens, int num_prompt,
+                    const int32_t* output_offsets, const int32_t* output_tokens, int num_output,
+                    const float* repetition, const float* frequency, const float* presence, const float* min_p,
+                    const float* temperature, float* out, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A7-A11  Arctic LSTM speculator (sum_lstm) — replaces ArcticLSTMSpeculator.generate_proposals /

@@ -676,8 +676,91 @@ def logprobs(B=64, V=128256, n=20, indexed=False, reps=3):
           f"x{min(ref) / max(hip):5.1f} (fastest torch / slowest hip)   same values and ranks: {same}", flush=True)
 
 
+def _torch_bin_counts(tokens, V):
+    """get_token_bin_counts_and_mask (vllm/model_executor/layers/utils.py, recalled): an int64 [B, V + 1] scatter-add."""
+    counts = torch.zeros((tokens.shape[0], V + 1), dtype=torch.long, device=tokens.device)
+    counts.scatter_add_(1, tokens, torch.ones_like(tokens))
+    counts = counts[:, :V]
+    return counts, counts > 0
+
+
+def _torch_edits(logits, mask, ban, bias, prompt, output, rep, freq, pres, min_p, temp):
+    """vLLM 0.9.2's path for the same step, restated in torch on the same GPU: the f32 copy, masked_fill_ of the allowed
+    mask, the index puts of bad words / min_tokens and of the bias (their index tensors are built outside the timed
+    region, vLLM builds them from Python lists every step), apply_penalties with its two bin-count matrices, and
+    apply_min_p on the softmax of the tempered rows (that division is the sampler's own in vLLM: it is counted here)."""
+    x = logits.float()
+    if mask is not None:
+        x.masked_fill_(mask, -float("inf"))
+    if ban is not None:
+        x[ban] = -float("inf")
+    if bias is not None:
+        x[bias[0], bias[1]] += bias[2]
+    if rep is not None:
+        V = x.shape[1]
+        _, prompt_mask = _torch_bin_counts(prompt, V)
+        out_counts, out_mask = _torch_bin_counts(output, V)
+        penalties = torch.where(prompt_mask | out_mask, rep.unsqueeze(1), 1.0)
+        x *= torch.where(x > 0, 1.0 / penalties, penalties)
+        x -= freq.unsqueeze(1) * out_counts
+        x -= pres.unsqueeze(1) * out_mask
+    if min_p is not None:
+        probs = torch.softmax(x / temp.unsqueeze(1), dim=-1)
+        x.masked_fill_(probs < min_p.unsqueeze(1) * probs.amax(dim=-1, keepdim=True), -float("inf"))
+    return x
+
+
+def edits(B=64, V=128256, case="all", n_prompt=4096, n_output=256, reps=3):
+    """aic_logits_edit (ops.edit_logits) against the torch restatement of vLLM's logits edits: same GPU, same inputs, the
+    two timed alternately `reps` times.  bf16 rows, histories of `n_prompt` + `n_output` tokens per row, 4 banned and 4
+    biased tokens per row, a 10 % allowed-token mask, min-p 0.1 at T = 0.8."""
+    g = torch.Generator(device=dev).manual_seed(0)
+    logits = (torch.randn(B, V, device=dev, generator=g) * 3).to(torch.bfloat16)
+    on = lambda name: case in (name, "all")
+    mask = (torch.rand(B, V, device=dev, generator=g) < 0.1) if on("mask") else None
+    rows4 = torch.arange(B, device=dev).repeat_interleave(4)
+    off4 = (torch.arange(B + 1, device=dev) * 4).to(torch.int32)
+    ban_tok = torch.randint(0, V, (B * 4,), device=dev, generator=g)
+    bias_tok = (torch.arange(B * 4, device=dev) * 7919) % V              # distinct within a row, as dict keys are
+    bias_val = torch.randn(B * 4, device=dev, generator=g)
+    prompt = torch.randint(0, V, (B, n_prompt), device=dev, generator=g)
+    prompt[:, -64:] = V                                                   # padding
+    output = torch.randint(0, V // 64, (B, n_output), device=dev, generator=g)      # repeats: counts above 1
+    off = lambda n: (torch.arange(B + 1, device=dev) * n).to(torch.int32)
+    f = lambda v: torch.full((B,), v, device=dev)
+    rep, freq, pres = (f(1.2), f(0.3), f(0.1)) if on("penalties") else (None, None, None)
+    min_p, temp = (f(0.1), f(0.8)) if on("min_p") else (None, None)
+    kw = dict(allowed_mask=mask, repetition=rep, frequency=freq, presence=pres, min_p=min_p, temperature=temp)
+    if on("ban"):
+        kw["ban"] = (off4, ban_tok.to(torch.int32))
+    if on("bias"):
+        kw["bias"] = (off4, bias_tok.to(torch.int32), bias_val)
+    if on("penalties"):
+        kw.update(prompt=(off(n_prompt), prompt.to(torch.int32).reshape(-1)), output=(off(n_output), output.to(torch.int32).reshape(-1)))
+    hip_fn = lambda: ops.edit_logits(logits, **kw)
+    ref_fn = lambda: _torch_edits(logits, mask, (rows4, ban_tok) if on("ban") else None,
+                                  (rows4, bias_tok, bias_val) if on("bias") else None, prompt, output, rep, freq, pres,
+                                  min_p, temp)
+    hip, ref = [], []
+    for _ in range(reps):
+        hip.append(timeit(hip_fn))
+        ref.append(timeit(ref_fn))
+    a, b = hip_fn(), ref_fn()
+    differ = int(((a != b) & ~(a.isnan() & b.isnan())).sum())
+    # HBM bytes of the HIP call: the 16-bit rows in, the f32 rows out, the mask, and min-p's second pass over the f32 rows
+    nbytes = B * V * (2 + 4 + (1 if on("mask") else 0) + (4 if on("min_p") else 0))
+    fmt = lambda v: " / ".join(f"{x:7.1f}" for x in v)
+    print(f"edits B={B} V={V} {case:9s}: hip {fmt(hip)} us ({nbytes / 1e6:6.1f} MB, {nbytes / 1e6 / min(hip):5.2f} TB/s)   "
+          f"torch {fmt(ref)} us   x{min(ref) / max(hip):5.1f} (fastest torch / slowest hip)   "
+          f"differing entries: {differ} of {B * V}", flush=True)
+
+
 if __name__ == "__main__":
     what = sys.argv[1:] or ["attn", "lstm", "rej"]
+    if "edits" in what:
+        for V in (128256, 201088):
+            for case in ("mask", "ban", "bias", "penalties", "min_p", "all"):
+                edits(V=V, case=case)
     if "logprobs" in what:
         for V in (128256, 201088):
             for indexed in (False, True):
