@@ -179,6 +179,14 @@ _SIGNATURES = {
                                             c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
                                             c_int, c_float, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_void_p, c_int,
                                             c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "aic_prefix_max_groups": (c_int, []),
+    # aic_verify_attention_dt's arguments before `stream`, then n_groups, three host arrays, two device arrays, stream
+    "aic_verify_attention_prefix_groups": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p,
+                                                   c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                                   c_int, c_int, c_int, c_int, c_float, c_void_p, c_int64, c_void_p,
+                                                   c_size_t, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
+                                                   c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                   c_void_p]),
     "aic_step_attention_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "aic_step_attention": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                    c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,

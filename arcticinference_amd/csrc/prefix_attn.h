@@ -37,4 +37,27 @@ int prefix_pick_splits(int num_tokens, int num_q_heads, int num_kv_heads, int pr
 // Launches the prefix body on `s`.  Arguments are those of a call aic_verify_attention_dt has accepted.
 int launch_prefix_attention(const PrefixArgs& a, hipStream_t s);
 
+// ---- groups of requests with a prefix each (aic_verify_attention_prefix_groups) ----
+constexpr int kPrefixMaxGroups = 16;
+
+struct PrefixGroupsArgs {
+  PrefixArgs base;                    // table = the call's block table (every row); prefix_len unused; n_splits of the call
+  int n_groups;                       // 1 .. kPrefixMaxGroups, every one with a prefix of at least one tile
+  int prefix_len[kPrefixMaxGroups];   // positive multiples of 32
+  int leader[kPrefixMaxGroups];       // request whose block-table row is the group's prefix table
+  int token_start[kPrefixMaxGroups];  // first entry of the group in token_index
+  int n_tokens[kPrefixMaxGroups];
+  const int32_t* token_index;         // device: token rows of the call, sorted by group
+  const int32_t* req_prefix_len;      // device int32[batch]: a request whose length rounds to 0 gets empty prefix slots
+  const int32_t* query_start_loc;     // device int32[batch + 1]
+  int batch;
+  int max_blocks;                     // columns of the block table
+};
+
+// One split count for the call, from the groups' row blocks and the longest prefix; rules as prefix_pick_splits.
+int prefix_groups_pick_splits(const PrefixGroupsArgs& a, int max_slots, int n_cus);
+
+// Launches the grouped prefix body on `s`: slots 0 .. n_splits - 1 of EVERY row of the call are written.
+int launch_prefix_groups_attention(const PrefixGroupsArgs& a, hipStream_t s);
+
 }  // namespace aic

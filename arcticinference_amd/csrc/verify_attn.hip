@@ -24,6 +24,7 @@
 //     back transposed with ds_read_b64_tr_b16 as the MFMA A operand.
 // Partials (m, l, unnormalised O) per (split, wave) go to a workspace; a second kernel merges them.
 #include <hip/hip_runtime.h>
+#include <climits>
 #include <type_traits>
 
 #include <algorithm>
@@ -108,8 +109,21 @@ struct AttnParams {
 // first token of the range a request's rows can see, rounded down to a tile: 0 without a window — or, in the PFX copies of
 // the bodies (a call with a shared prefix), the prefix length (clamped to the context, so that a request that breaks the call's precondition and is shorter
 // than the prefix gets an empty range, not a negative one)
+// What the PFX copies of the bodies get: AttnParams with one field appended, so that no field of AttnParams moves and the
+// default kernels — the one-grid kernel takes two AttnParams by value — keep their argument layout to the byte.
+// req_begin (aic_verify_attention_prefix_groups): device int32[batch], the prefix length of each request's group (0: in no
+// group), rounded down to a tile and clamped to the context here; nullptr: the call's one prefix, -window, as before.
+// The bodies take `const AttnParams&`; a PFX body is only ever handed the AttnParams base of an AttnParamsPfx.
+struct AttnParamsPfx : AttnParams {
+  const int32_t* req_begin;
+};
+
 template <bool PFX = false>
-__device__ __forceinline__ int window_begin(const AttnParams& P, int ctx, int q_len) {
+__device__ __forceinline__ int window_begin(const AttnParams& P, int ctx, int q_len, int req) {
+  if constexpr (PFX) {
+    const int32_t* rb = static_cast<const AttnParamsPfx&>(P).req_begin;
+    if (rb) return min(max(rb[req], 0) & ~(kTile - 1), ctx);
+  }
   if (P.window <= 0) return PFX ? min(-P.window, ctx) : 0;
   const int lo = ctx - q_len - P.window + 1;
   return lo > 0 ? (lo & ~(kTile - 1)) : 0;
@@ -286,7 +300,7 @@ __device__ __forceinline__ void verify_attn_body(const AttnParams& P, uint4* v_l
 
   const int n_parts = P.n_splits * R;
   const int part = by * R + range;
-  const int t_lo = window_begin<PFX>(P, ctx, q_len);   // 0 unless the layer has a sliding window or the call a shared prefix
+  const int t_lo = window_begin<PFX>(P, ctx, q_len, req);   // 0 unless the layer has a sliding window or the call a shared prefix
   const int wnd = P.window > 0 ? P.window : (1 << 30);
   const int tiles_total = (ctx - t_lo + kTile - 1) / kTile;
   int t_begin, t_end;
@@ -700,11 +714,12 @@ __device__ __forceinline__ void verify_attn_body_dual(const AttnParams& P, uint4
 }
 
 // MTQ = 0: the per-workgroup choice above
-// PFX: the copy a call with a shared prefix launches (aic_verify_attention_prefix): its token ranges start at the prefix
-// length carried in AttnParams.window (negative).  The default instantiations (PFX = false) know nothing of it and are, to
+// PFX: the copy a call with a shared prefix launches (aic_verify_attention_prefix, aic_verify_attention_prefix_groups): its
+// token ranges start at the prefix length carried in AttnParams.window (negative), or at each request's own
+// (AttnParamsPfx::req_begin).  The default instantiations (PFX = false) know nothing of it and are, to
 // the instruction, what they were before shared prefixes existed.
 template <int MTQ, int HPW, bool KV8, int NW = 4, int HD = kD, typename E = ElemBf16, bool PFX = false>
-__global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((MTQ == 1 && NW == 4) ? 3 : 2, (MTQ == 1 && NW == 4) ? 3 : 2))) verify_attn_kernel(AttnParams P) {
+__global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((MTQ == 1 && NW == 4) ? 3 : 2, (MTQ == 1 && NW == 4) ? 3 : 2))) verify_attn_kernel(std::conditional_t<PFX, AttnParamsPfx, AttnParams> P) {
   __shared__ uint4 v_lds_raw[ShortLds<MTQ == 0 ? 2 : MTQ, NW, HD>::kU4];
   if constexpr (MTQ == 0)
     verify_attn_body_dual<HPW, KV8, NW, HD, E, PFX>(P, v_lds_raw, blockIdx.x, blockIdx.y);
@@ -961,7 +976,7 @@ __device__ __forceinline__ void verify_attn_long4_body(const AttnParams& P, uint
   const int row_base = bz * (4 * RT * 16);
   if (row_base >= n_rows) return;
 
-  const int t_lo = window_begin<PFX>(P, ctx, q_len);
+  const int t_lo = window_begin<PFX>(P, ctx, q_len, req);
   const int wnd = P.window > 0 ? P.window : (1 << 30);
   const int tiles_total = (ctx - t_lo + kTile - 1) / kTile;
   const int tiles_per_part = (tiles_total + P.n_splits - 1) / P.n_splits;
@@ -1395,7 +1410,7 @@ __device__ __forceinline__ void verify_attn_long4_body(const AttnParams& P, uint
 }
 
 template <bool KV8, int D = 128, bool TR = false, typename E = ElemBf16, bool PFX = false>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) verify_attn_long4_kernel(AttnParams P) {
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) verify_attn_long4_kernel(std::conditional_t<PFX, AttnParamsPfx, AttnParams> P) {
   __shared__ __attribute__((aligned(1024))) uint4 lds[kLong4LdsU4];
   verify_attn_long4_body<KV8, D, TR, E, PFX>(P, lds, blockIdx.x, blockIdx.y, blockIdx.z);
 }
@@ -1767,15 +1782,21 @@ static int verify_attention_impl(const void* q, int64_t q_stride, const void* k_
                                  int64_t out_stride, void* workspace, size_t workspace_bytes, int max_seq_len_full,
                                  const int32_t* short_reqs, int n_short, const int32_t* long_reqs, int n_long,
                                  int sliding_window, const float* sinks, void* stream, int prefix_len = 0,
-                                 const int32_t* prefix_table = nullptr) {
+                                 const int32_t* prefix_table = nullptr, PrefixGroupsArgs* groups = nullptr,
+                                 int groups_min_begin = 0) {
   // prefix_len > 0 (a multiple of the tile; aic_verify_attention_prefix): keys [0, prefix_len) of every request are the
   // pages of prefix_table and go through the prefix body, the bodies launched here start at prefix_len
+  // groups (aic_verify_attention_prefix_groups; prefix_len is then 0): the same per group of requests — the grouped prefix
+  // body serves keys [0, P_g) of group g's rows, the bodies launched here start at each request's own length
+  // (groups->req_prefix_len, read on the device); groups_min_begin = the smallest begin of any request of the call, 0 when
+  // one is in no group.  Only the launch fields of *groups are filled in here.
+  const bool has_prefix = prefix_len > 0 || groups != nullptr;
   constexpr bool kTraceable = std::is_same<E, ElemBf16>::value;
   AIC_REQUIRE(sliding_window >= 0, "sliding_window must be >= 0 (0 = none)");
   // what a request streams at most: the whole context, or — sliding window — the window plus the draft and tile slack
   // — or, with a shared prefix, what lies behind it
   const int max_seq_len = sliding_window > 0 ? std::min(max_seq_len_full, sliding_window + max_q_len + kTile)
-                                             : max_seq_len_full - prefix_len;
+                                             : max_seq_len_full - (groups ? groups_min_begin : prefix_len);
   AIC_REQUIRE(q && k_cache && v_cache && block_table && seq_lens && query_start_loc && out && workspace,
               "null pointer argument to aic_verify_attention");
   AIC_REQUIRE(batch > 0 && num_tokens > 0 && max_q_len > 0 && num_q_heads > 0 && num_kv_heads > 0 && block_size > 0 &&
@@ -1823,7 +1844,7 @@ static int verify_attention_impl(const void* q, int64_t q_stride, const void* k_
     n_splits = pick_splits(batch * hgroups, max_seq_len, wave_heads ? 2 : 8, 1, 0);
   }
   const int hgroups_s = num_kv_heads / hpw;              // head groups of the short launch
-  const bool direct = split_lists && n_short > 0 && n_splits == 1 && prefix_len == 0;   // a prefix: every row needs the merge
+  const bool direct = split_lists && n_short > 0 && n_splits == 1 && !has_prefix;   // a prefix: every row needs the merge
   int n_splits_long = (split_lists && n_long > 0) ? pick_splits(n_long * num_kv_heads, max_seq_len, mixed ? 4 : 8, 2) : 0;
   // The long part of a mixed call: its workgroups start first and should end with the short ones.  Per-workgroup traces
   // (tools/microbench.py sptrace / longsplits, 4224-token contexts, profiles/r02_long_splits.txt): a short workgroup takes
@@ -1857,7 +1878,7 @@ static int verify_attention_impl(const void* q, int64_t q_stride, const void* k_
     const bool want = g_force_sequential >= 0 ? g_force_sequential == 1 : (fit == 1 && n_splits_long >= 2);
     // (a call with a shared prefix always: the one-grid kernel has no prefix-carrying copy — it is the project's largest
     // and slowest to compile, and the bodies it is made of exist as such copies on their own)
-    if (fit < 1 || want || prefix_len > 0) {
+    if (fit < 1 || want || has_prefix) {
       sequential = true;
       n_splits_long = pick_splits(n_long * num_kv_heads, max_seq_len, 8, 2);
     }
@@ -1868,13 +1889,19 @@ static int verify_attention_impl(const void* q, int64_t q_stride, const void* k_
   // live, and slot 0 never holds l = -1 (a prefix partial's sum is positive; direct output is off).  At most 64 in all,
   // at least one of each kind, and the suffix launches give way to the workspace before the prefix launch does.
   int n_pre = 0;
-  if (prefix_len > 0) {
+  if (has_prefix) {
     while (std::max(n_splits, n_splits_long) > 63) {
       if (n_splits > 63) --n_splits;
       if (n_splits_long > 63) --n_splits_long;
     }
-    n_pre = prefix_pick_splits(num_tokens, num_q_heads, num_kv_heads, prefix_len, 64 - std::max(n_splits, n_splits_long),
-                               cu_count());
+    if (groups) {
+      groups->base.num_q_heads = num_q_heads;
+      groups->base.num_kv_heads = num_kv_heads;
+      n_pre = prefix_groups_pick_splits(*groups, 64 - std::max(n_splits, n_splits_long), cu_count());
+    } else {
+      n_pre = prefix_pick_splits(num_tokens, num_q_heads, num_kv_heads, prefix_len, 64 - std::max(n_splits, n_splits_long),
+                                 cu_count());
+    }
     while (n_pre > 1 && !fits(n_pre + std::max(n_splits, n_splits_long))) --n_pre;
   }
   while (n_splits > 1 && !fits(n_pre + n_splits)) --n_splits;
@@ -1932,6 +1959,7 @@ static int verify_attention_impl(const void* q, int64_t q_stride, const void* k_
   // 86.9 / 75.1; plain call 144 / 83).  The fork and join cost a small call ~10 us (8 requests: 37.9 -> 47.8 us against
   // 33 plain) — calls the prefix form loses either way.
   SideStream* pside = nullptr;
+  PrefixArgs single_prefix_args;
   // whatever ends the call — an error return below included — the call's stream waits for the side stream first: the
   // prefix launch writes the caller's workspace, and the caller may reuse it as soon as `stream` says the call is over
   struct PrefixJoin {
@@ -1944,16 +1972,16 @@ static int verify_attention_impl(const void* q, int64_t q_stride, const void* k_
       (void)hipStreamWaitEvent(s, side->join, 0);
     }
   } prefix_join{pside, s};
-  if (prefix_len > 0) {
+  if (has_prefix) {
     if ((rc = side_stream(&pside)) != AIC_OK) return rc;
     AIC_HIP_TRY(hipEventRecord(pside->fork, s));
     prefix_join.forked = true;
     AIC_HIP_TRY(hipStreamWaitEvent(pside->stream, pside->fork, 0));
-    PrefixArgs A;
+    PrefixArgs& A = groups ? groups->base : single_prefix_args;
     A.q = q;
     A.k_cache = k_cache;
     A.v_cache = v_cache;
-    A.table = prefix_table;
+    A.table = groups ? block_table : prefix_table;
     A.k_scale = k_scale;
     A.v_scale = v_scale;
     A.ws_o = ws_o_all;
@@ -1970,26 +1998,41 @@ static int verify_attention_impl(const void* q, int64_t q_stride, const void* k_
     A.sm_scale = sm_scale;
     A.kv8 = kv8;
     A.f16 = std::is_same<E, ElemF16>::value;
-    if ((rc = launch_prefix_attention(A, pside->stream)) != AIC_OK) return rc;
+    if (groups) {
+      groups->query_start_loc = query_start_loc;
+      groups->batch = batch;
+      groups->max_blocks = max_blocks_per_seq;
+      if ((rc = launch_prefix_groups_attention(*groups, pside->stream)) != AIC_OK) return rc;
+    } else if ((rc = launch_prefix_attention(A, pside->stream)) != AIC_OK) {
+      return rc;
+    }
     // (a head-size-64 call with long drafts records this event again behind its long part, later on the same in-order
     // stream: the wait below then covers both)
     AIC_HIP_TRY(hipEventRecord(pside->join, pside->stream));
     prefix_join.recorded = true;
   }
   // short / generic kernel for (row tiles, heads per workgroup, cache dtype)
+  // the argument of a PFX copy: the launch's AttnParams and the requests' own begins (groups) or none (one prefix)
+  auto with_begin = [&](const AttnParams& p) {
+    AttnParamsPfx x;
+    static_cast<AttnParams&>(x) = p;
+    x.req_begin = groups ? groups->req_prefix_len : nullptr;
+    return x;
+  };
   auto launch_short = [&](int mtq_, int hpw_, dim3 grid_) {
-#define AIC_SHORT_P(MTQ_, HPW_, PFX_)                                                          \
+#define AIC_SHORT_P(MTQ_, HPW_, PFX_, P_)                                                      \
   if (d64)                                                                                     \
-    launch(verify_attn_kernel<MTQ_, HPW_, false, 4, 64, E, PFX_>, grid_, dim3(256), s, P);     \
+    launch(verify_attn_kernel<MTQ_, HPW_, false, 4, 64, E, PFX_>, grid_, dim3(256), s, P_);    \
   else if (kv8)                                                                                \
-    launch(verify_attn_kernel<MTQ_, HPW_, true, 4, kD, E, PFX_>, grid_, dim3(256), s, P);      \
+    launch(verify_attn_kernel<MTQ_, HPW_, true, 4, kD, E, PFX_>, grid_, dim3(256), s, P_);     \
   else                                                                                         \
-    launch(verify_attn_kernel<MTQ_, HPW_, false, 4, kD, E, PFX_>, grid_, dim3(256), s, P);
+    launch(verify_attn_kernel<MTQ_, HPW_, false, 4, kD, E, PFX_>, grid_, dim3(256), s, P_);
 #define AIC_SHORT(MTQ_, HPW_)                                                                  \
-  if (prefix_len > 0) {                                                                        \
-    AIC_SHORT_P(MTQ_, HPW_, true)                                                              \
+  if (has_prefix) {                                                                            \
+    const AttnParamsPfx PX = with_begin(P);                                                    \
+    AIC_SHORT_P(MTQ_, HPW_, true, PX)                                                          \
   } else {                                                                                     \
-    AIC_SHORT_P(MTQ_, HPW_, false)                                                             \
+    AIC_SHORT_P(MTQ_, HPW_, false, P)                                                          \
   }
     if (mtq_ == 0) {
       if (hpw_ == 4) { AIC_SHORT(0, 4) } else if (hpw_ == 2) { AIC_SHORT(0, 2) } else { AIC_SHORT(0, 1) }
@@ -2110,7 +2153,7 @@ static int verify_attention_impl(const void* q, int64_t q_stride, const void* k_
       dim3 grid(static_cast<unsigned>(n_long * num_kv_heads), n_splits_long, (max_rows + per_block_rows - 1) / per_block_rows);
       bool traced = false;
       if constexpr (kTraceable) {
-        if (g_attn_ptrace && prefix_len == 0 && !d64 && !kv8 && n_short == 0 && static_cast<int>(grid.x * grid.y * grid.z) * 8 <= g_attn_ptrace_cap) {
+        if (g_attn_ptrace && !has_prefix && !d64 && !kv8 && n_short == 0 && static_cast<int>(grid.x * grid.y * grid.z) * 8 <= g_attn_ptrace_cap) {
           PL.ptrace = g_attn_ptrace;   // debug: per-wave cycle accounting of a long-only call (tools/microbench.py longphases)
           PL.ptrace_stride = static_cast<int>(grid.x) | (static_cast<int>(grid.y) << 16);
           launch(verify_attn_long4_kernel<false, 128, true>, grid, dim3(256), s, PL);
@@ -2118,13 +2161,14 @@ static int verify_attention_impl(const void* q, int64_t q_stride, const void* k_
         }
       }
       if (traced) {
-      } else if (prefix_len > 0) {
+      } else if (has_prefix) {
+        const AttnParamsPfx PX = with_begin(PL);
         if (d64)
-          launch(verify_attn_long4_kernel<false, 64, false, E, true>, grid, dim3(256), overlap ? side->stream : s, PL);
+          launch(verify_attn_long4_kernel<false, 64, false, E, true>, grid, dim3(256), overlap ? side->stream : s, PX);
         else if (kv8)
-          launch(verify_attn_long4_kernel<true, 128, false, E, true>, grid, dim3(256), overlap ? side->stream : s, PL);
+          launch(verify_attn_long4_kernel<true, 128, false, E, true>, grid, dim3(256), overlap ? side->stream : s, PX);
         else
-          launch(verify_attn_long4_kernel<false, 128, false, E, true>, grid, dim3(256), overlap ? side->stream : s, PL);
+          launch(verify_attn_long4_kernel<false, 128, false, E, true>, grid, dim3(256), overlap ? side->stream : s, PX);
       } else if (d64)
         launch(verify_attn_long4_kernel<false, 64, false, E>, grid, dim3(256), overlap ? side->stream : s, PL);
       else if (kv8)
@@ -2236,6 +2280,81 @@ int aic_verify_attention_prefix(const void* q, int64_t q_stride, const void* k_c
                                          num_q_heads, num_kv_heads, head_size, block_size, sm_scale, out, out_stride,
                                          workspace, workspace_bytes, max_seq_len, short_reqs, n_short, long_reqs, n_long,
                                          sliding_window, sinks, stream, prefix_len, prefix_block_table);
+}
+
+int aic_prefix_max_groups(void) { return kPrefixMaxGroups; }
+
+// The same call for a step whose requests fall into groups with a shared prefix EACH, beside requests that share nothing
+// (include/arctic_hip.h; the one attention call of a step, the reference's arctic_inference/vllm/ulysses.py:510, on steps
+// vLLM's use_cascade does not mark).  The group arrays are host data except group_token_index and req_prefix_len.
+int aic_verify_attention_prefix_groups(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache,
+                                       int64_t block_stride, int kv_dtype, const float* k_scale, const float* v_scale,
+                                       const int32_t* block_table, int max_blocks_per_seq, const int32_t* seq_lens,
+                                       const int32_t* query_start_loc, int batch, int num_tokens, int max_q_len,
+                                       int num_q_heads, int num_kv_heads, int head_size, int block_size, float sm_scale,
+                                       void* out, int64_t out_stride, void* workspace, size_t workspace_bytes,
+                                       int max_seq_len, const int32_t* short_reqs, int n_short, const int32_t* long_reqs,
+                                       int n_long, int sliding_window, const float* sinks, int q_dtype, int n_groups,
+                                       const int32_t* group_prefix_len, const int32_t* group_leader,
+                                       const int32_t* group_token_start, const int32_t* group_token_index,
+                                       const int32_t* req_prefix_len, void* stream) {
+  AIC_REQUIRE(n_groups >= 0 && n_groups <= kPrefixMaxGroups, "n_groups %d outside 0 .. %d", n_groups, kPrefixMaxGroups);
+  PrefixGroupsArgs A;
+  A.n_groups = 0;
+  int min_begin = 0;
+  if (n_groups > 0) {
+    AIC_REQUIRE(group_prefix_len && group_leader && group_token_start && group_token_index && req_prefix_len,
+                "prefix groups need all five group arrays");
+    AIC_REQUIRE(group_token_start[0] >= 0, "group_token_start must begin at or above 0");
+    int max_p = 0, covered = 0;
+    min_begin = INT_MAX;
+    for (int g = 0; g < n_groups; ++g) {
+      AIC_REQUIRE(group_prefix_len[g] >= 0, "group_prefix_len[%d] must be >= 0", g);
+      AIC_REQUIRE(group_leader[g] >= 0 && group_leader[g] < batch, "group_leader[%d] = %d outside the batch of %d", g,
+                  group_leader[g], batch);
+      AIC_REQUIRE(group_token_start[g + 1] >= group_token_start[g], "group_token_start must not decrease");
+      const int p = group_prefix_len[g] & ~(kTile - 1), n = group_token_start[g + 1] - group_token_start[g];
+      if (p == 0 || n == 0) continue;   // below one tile, or nobody in it: treated as ungrouped
+      A.prefix_len[A.n_groups] = p;
+      A.leader[A.n_groups] = group_leader[g];
+      A.token_start[A.n_groups] = group_token_start[g];
+      A.n_tokens[A.n_groups] = n;
+      ++A.n_groups;
+      max_p = std::max(max_p, p);
+      min_begin = std::min(min_begin, p);
+      covered += n;
+    }
+    AIC_REQUIRE(group_token_start[n_groups] <= num_tokens, "group_token_start ends at %d, above the call's %d tokens",
+                group_token_start[n_groups], num_tokens);
+    AIC_REQUIRE(max_seq_len > max_p, "every member must hold its query tokens behind its group's prefix "
+                "(max_seq_len %d, longest prefix %d)", max_seq_len, max_p);
+    if (covered < num_tokens) min_begin = 0;   // a request in no group starts at 0
+    if (sliding_window > 0) {
+      set_error("prefix groups with a sliding window are not supported");
+      return AIC_ERR_UNSUPPORTED;
+    }
+  }
+  if (A.n_groups == 0 || batch == 0 || num_tokens == 0)   // nothing for the prefix body: exactly the plain call
+    return aic_verify_attention_dt(q, q_stride, k_cache, v_cache, block_stride, kv_dtype, k_scale, v_scale, block_table,
+                                   max_blocks_per_seq, seq_lens, query_start_loc, batch, num_tokens, max_q_len, num_q_heads,
+                                   num_kv_heads, head_size, block_size, sm_scale, out, out_stride, workspace, workspace_bytes,
+                                   max_seq_len, short_reqs, n_short, long_reqs, n_long, sliding_window, sinks, q_dtype,
+                                   stream);
+  if (const int rc = attn_check_dtypes(q_dtype, kv_dtype); rc != AIC_OK) return rc;
+  A.token_index = group_token_index;
+  A.req_prefix_len = req_prefix_len;
+  const bool kv8 = kv_dtype == AIC_DT_FP8_E4M3;
+  if (q_dtype == AIC_DT_F16)
+    return verify_attention_impl<ElemF16>(q, q_stride, k_cache, v_cache, block_stride, kv8, k_scale, v_scale, block_table,
+                                          max_blocks_per_seq, seq_lens, query_start_loc, batch, num_tokens, max_q_len,
+                                          num_q_heads, num_kv_heads, head_size, block_size, sm_scale, out, out_stride,
+                                          workspace, workspace_bytes, max_seq_len, short_reqs, n_short, long_reqs, n_long,
+                                          sliding_window, sinks, stream, 0, nullptr, &A, min_begin);
+  return verify_attention_impl<ElemBf16>(q, q_stride, k_cache, v_cache, block_stride, kv8, k_scale, v_scale, block_table,
+                                         max_blocks_per_seq, seq_lens, query_start_loc, batch, num_tokens, max_q_len,
+                                         num_q_heads, num_kv_heads, head_size, block_size, sm_scale, out, out_stride,
+                                         workspace, workspace_bytes, max_seq_len, short_reqs, n_short, long_reqs, n_long,
+                                         sliding_window, sinks, stream, 0, nullptr, &A, min_begin);
 }
 
 // ---- a run of layers as one graph launch ------------------------------------------------------------------------------

@@ -391,6 +391,82 @@ def _check_shared_prefix(shared_prefix_len: int, table: Optional[torch.Tensor], 
                                  "(every query token must lie behind the shared prefix)")
 
 
+def prefix_max_groups() -> int:
+    """How many groups one aic_verify_attention_prefix_groups call takes."""
+    return int(N.lib().aic_prefix_max_groups())
+
+
+class PrefixGroups:
+    """The groups of a step for verify_attention(..., prefix_groups=): requests that begin with the same tokens held in
+    the same pages, a prefix per group, beside requests that share nothing (aic_verify_attention_prefix_groups).
+    `req_group[i]` is request i's group index, or -1; `group_prefix_len[g]` the tokens group g's members share (served
+    rounded down to a multiple of 32); `q_lens_host` the per-request query lengths.  The leader of a group — the request
+    whose block-table row names the group's pages — is its first member.  The five arrays of the call are laid out in one
+    host buffer (pinned when `device` is a GPU) and the two the kernels read go up in one copy; build it once per step and
+    hand it to every layer's call.  ValueError, before anything touches a device: more groups than
+    prefix_max_groups(), a group index out of range, a group without members, a negative length, no `q_lens_host`."""
+
+    def __init__(self, req_group: Sequence[int], group_prefix_len: Sequence[int], q_lens_host: Sequence[int], device):
+        import numpy as np
+        if q_lens_host is None:
+            raise ValueError("PrefixGroups needs q_lens_host (the per-request query lengths)")
+        rg = np.asarray(req_group, dtype=np.int64).reshape(-1)
+        gl = np.asarray(group_prefix_len, dtype=np.int64).reshape(-1)
+        ql = np.asarray(q_lens_host, dtype=np.int64).reshape(-1)
+        n, B = int(gl.size), int(rg.size)
+        if ql.size != B:
+            raise ValueError(f"req_group names {B} requests, q_lens_host {ql.size}")
+        if n > prefix_max_groups():
+            raise ValueError(f"{n} prefix groups: one call takes at most {prefix_max_groups()}")
+        if B and (int(rg.min()) < -1 or int(rg.max()) >= n):
+            bad = int(np.flatnonzero((rg < -1) | (rg >= n))[0])
+            raise ValueError(f"request {bad}: group index {int(rg[bad])} out of range (-1, or 0 .. {n - 1})")
+        if n and int(gl.min()) < 0:
+            raise ValueError("group_prefix_len must be >= 0")
+        members = np.bincount(rg[rg >= 0], minlength=n) if n else np.zeros(0, dtype=np.int64)
+        if n and int(members.min()) == 0:
+            raise ValueError(f"prefix group {int(np.argmin(members))} has no members")
+        qsl = np.concatenate([[0], np.cumsum(ql)])
+        tok_req = np.repeat(np.arange(B), ql)                       # request of every token row
+        tok_grp = rg[tok_req] if B else np.zeros(0, dtype=np.int64)
+        grouped = np.flatnonzero(tok_grp >= 0)
+        token_index = grouped[np.argsort(tok_grp[grouped], kind="stable")]
+        start = np.concatenate([[0], np.cumsum(np.bincount(tok_grp[grouped], minlength=n))]) if n else np.zeros(1)
+        leader = np.array([int(np.flatnonzero(rg == g)[0]) for g in range(n)], dtype=np.int64)
+        req_len = np.where(rg >= 0, gl[np.maximum(rg, 0)] if n else 0, 0)
+        device = torch.device(device)
+        parts = [gl, leader, start, token_index, req_len]
+        sizes = [int(np.size(x)) for x in parts]
+        host = torch.empty(sum(sizes), dtype=torch.int32, pin_memory=device.type == "cuda")
+        hv = host.numpy()
+        offs = np.concatenate([[0], np.cumsum(sizes)])
+        for x, o in zip(parts, offs):
+            hv[o:o + np.size(x)] = x
+        self._host = host                                           # keeps the three host arrays alive
+        self.group_prefix_len, self.group_leader, self.group_token_start = (hv[offs[i]:offs[i + 1]] for i in range(3))
+        dev = host[int(offs[3]):].to(device, non_blocking=True)     # the one copy of the step
+        self.group_token_index, self.req_prefix_len = dev[:sizes[3]], dev[sizes[3]:]
+        self.n_groups, self.batch, self.num_tokens = n, B, int(qsl[-1])
+        self.req_group, self.q_lens = rg, ql
+        self.max_prefix_len = int(gl.max()) if n else 0
+
+    def check_call(self, batch: int, num_tokens: int, sliding_window: int, max_seq_len: int, seq_lens_host) -> None:
+        """The argument rules of the grouped call that can be told on the host (ValueError, before the device check)."""
+        if sliding_window > 0:
+            raise ValueError("prefix groups are not served on a layer with a sliding window")
+        if batch != self.batch or num_tokens != self.num_tokens:
+            raise ValueError(f"prefix_groups describes {self.batch} requests / {self.num_tokens} tokens, the call has "
+                             f"{batch} / {num_tokens}")
+        if self.n_groups and max_seq_len <= (self.max_prefix_len & ~31):
+            raise ValueError(f"max_seq_len {max_seq_len} leaves no query token behind a group prefix of "
+                             f"{self.max_prefix_len}")
+        if seq_lens_host is not None:
+            for i, (s_, ql, g) in enumerate(zip(seq_lens_host, self.q_lens, self.req_group)):
+                if g >= 0 and int(s_) - int(ql) < int(self.group_prefix_len[g]):
+                    raise ValueError(f"request {i}: seq_len {int(s_)} - q_len {int(ql)} < its group's prefix length "
+                                     f"{int(self.group_prefix_len[g])} (every query token must lie behind the prefix)")
+
+
 def verify_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor,
                      seq_lens: torch.Tensor, query_start_loc: torch.Tensor, max_q_len: int, max_seq_len: int,
                      sm_scale: float, out: Optional[torch.Tensor] = None, num_splits_max: int = 64,
@@ -399,7 +475,8 @@ def verify_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
                      stream: Optional[int] = None, sliding_window: int = 0,
                      sinks: Optional[torch.Tensor] = None, shared_prefix_len: int = 0,
                      prefix_block_table: Optional[torch.Tensor] = None,
-                     seq_lens_host: Optional[Sequence[int]] = None) -> torch.Tensor:
+                     seq_lens_host: Optional[Sequence[int]] = None,
+                     prefix_groups: Optional[PrefixGroups] = None) -> torch.Tensor:
     """q [T, Hq, D] in bf16 or fp16 (token stride may exceed Hq*D: a view into an all-to-all receive buffer works),
     caches [num_blocks, block_size, Hkv, D] in q's dtype, or float8_e4m3fn with per-tensor `k_scale` / `v_scale`
     (device scalars, the scales A16 divided by); returns [T, Hq, D] in q's dtype (aic_verify_attention_dt).  `q_lens_host` (the per-request query
@@ -411,9 +488,20 @@ def verify_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     same pages (prefix caching), and those keys are read once for the call (aic_verify_attention_prefix: cascade
     attention) instead of once per request.  PRECONDITION: seq_len - q_len >= P for every request; checked here when the
     lengths are on the host (`q_lens_host` together with `seq_lens_host`, or with a `seq_lens` that is a CPU tensor),
-    otherwise the caller's to keep.  Not with a sliding window.  0 (the default) is the call as it always was."""
+    otherwise the caller's to keep.  Not with a sliding window.  0 (the default) is the call as it always was.
+    `prefix_groups` (a PrefixGroups of the step): groups of requests with a shared prefix each, beside requests that share
+    nothing (aic_verify_attention_prefix_groups); the same precondition per group (a member's block-table columns below
+    its group's length are its leader's), checked here when `seq_lens_host` or a CPU `seq_lens` is given.  Not together
+    with `shared_prefix_len`, not with a sliding window.  None (the default) makes exactly the calls made without it."""
     qd, kvd = _attn_dtypes(q, k_cache, v_cache, out)
     shared_prefix_len = int(shared_prefix_len or 0)
+    if prefix_groups is not None:
+        if shared_prefix_len:
+            raise ValueError("prefix_groups and shared_prefix_len are two forms of the call: give one")
+        host = seq_lens_host
+        if host is None and not seq_lens.is_cuda:
+            host = seq_lens.tolist()
+        prefix_groups.check_call(int(seq_lens.numel()), int(q.shape[0]), int(sliding_window or 0), int(max_seq_len), host)
     if shared_prefix_len:
         _check_shared_prefix(shared_prefix_len, prefix_block_table, q, int(k_cache.shape[1]), int(sliding_window or 0),
                              q_lens_host, seq_lens_host, seq_lens, int(max_seq_len))
@@ -431,6 +519,18 @@ def verify_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     if req_split is None and q_lens_host is not None:
         req_split = split_requests(q_lens_host, Hq // Hkv, q.device)
     short, n_short, long_, n_long = req_split if req_split is not None else (None, 0, None, 0)
+    if prefix_groups is not None:
+        g = prefix_groups
+        _need_cuda(g.group_token_index, g.req_prefix_len)
+        N.check(N.lib().aic_verify_attention_prefix_groups(
+            q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(0), kvd, _ptr(k_scale),
+            _ptr(v_scale), block_table.data_ptr(), block_table.size(1), seq_lens.data_ptr(), query_start_loc.data_ptr(), B,
+            T, int(max_q_len), Hq, Hkv, D, bs, float(sm_scale), out.data_ptr(), out.stride(0), ws.data_ptr(), ws.numel(),
+            int(max_seq_len), _ptr(short) if n_short else None, n_short, _ptr(long_) if n_long else None, n_long, 0,
+            _ptr(sinks), qd, g.n_groups, g.group_prefix_len.ctypes.data, g.group_leader.ctypes.data,
+            g.group_token_start.ctypes.data, g.group_token_index.data_ptr(), g.req_prefix_len.data_ptr(),
+            N.current_stream_ptr() if stream is None else stream))
+        return out
     if shared_prefix_len:
         _need_cuda(prefix_block_table)
         N.check(N.lib().aic_verify_attention_prefix(

@@ -370,7 +370,15 @@ def build_model_runner_patch():
 
             model_kwargs = self._arctic_model_inputs(scheduler_output, n_sched, n_input, intermediate_tensors)
             skip_cuda_graphs = self.full_cuda_graph and not attention_cuda_graphs
-            step_context.publish(num_scheduled_tokens_np, use_shift)    # q_len per request: the attention patch's split lists
+            if step_context.prefix_groups_switch():
+                # ARCTIC_INFERENCE_HIP_PREFIX_GROUPS: the host block table and the cached-token counts, from which the
+                # attention patch finds the groups of requests that share a prefix (runner_logic.prefix_groups)
+                ib = self.input_batch
+                step_context.publish(num_scheduled_tokens_np, use_shift, block_table=getattr(ib, "block_table", None),
+                                     num_computed=getattr(ib, "num_computed_tokens_cpu", None),
+                                     block_size=getattr(self, "block_size", None))
+            else:
+                step_context.publish(num_scheduled_tokens_np, use_shift)    # q_len per request: the attention patch's split lists
             try:
                 with set_forward_context(attn_metadata, self.vllm_config, num_tokens=n_input,
                                          num_tokens_across_dp=num_tokens_across_dp, skip_cuda_graphs=skip_cuda_graphs):

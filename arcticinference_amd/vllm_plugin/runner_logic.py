@@ -234,3 +234,119 @@ def shared_prefix_len(meta, window: int, capturing: bool, switch_on: bool, num_k
         if items < (SHARED_PREFIX_MIN_ITEMS_FP8 if fp8 else SHARED_PREFIX_MIN_ITEMS):
             return 0
     return n
+
+
+PREFIX_GROUPS_ENV = "ARCTIC_INFERENCE_HIP_PREFIX_GROUPS"   # 1: steps whose requests share prefixes in groups (default off)
+PREFIX_GROUPS_MAX = 16               # aic_prefix_max_groups(): groups one call takes (a host test holds the two together)
+# From where on the plugin hands groups to aic_verify_attention_prefix_groups.  Measured on the MI355X (tools/microbench.py
+# prefixgroups, profiles/prefix_groups_microbench.txt; 64 requests x 4 query tokens, 4224-token contexts, 8 kv heads, both
+# forms alternating, medians of 5 windows; time of the grouped call / time of the plain call, the plain call's own
+# max - min spread 1.3 .. 6.1 us of ~144 (bf16) and 0.8 .. 7.0 of ~81 (fp8)):
+#   every request grouped, P = 2048:  bf16 1 x 64 0.81, 2 x 32 0.83, 4 x 16 0.84, 8 x 8 0.83, 16 x 4 0.95
+#                                     fp8  1 x 64 0.94, 2 x 32 0.95, 4 x 16 0.95, 8 x 8 0.93, 16 x 4 1.06
+#   2 x 32 with two lengths:          bf16 2048 / 3072 0.86, 1536 / 2560 0.92, 1024 / 3072 1.01
+#                                     fp8  2048 / 3072 1.02, 1536 / 2560 1.05, 1024 / 3072 1.11
+#   requests in no group:             bf16 2 x 24 + 16 1.20, 2 x 31 + 2 1.18;  fp8 1.34, 1.26
+# MIN_MEMBERS: the smallest measured members per group at which the grouped call beats the plain one by more than twice the
+# plain call's spread, per cache kind (bf16: 4 members 139.0 against 146.9 +- 1.6 us; fp8: 4 lose, 8 win 77.0 against 82.5
+# +- 1.4).  What the group size does not decide: the suffix launch lasts as long as its longest request, so ONE request
+# that keeps (nearly) its whole context — a request in no group, or a group with a short prefix beside long ones — costs
+# the call all it saved, and the prefix launch on top (two ungrouped requests of 64: 1.18).  MAX_SUFFIX_FRACTION: the
+# largest measured (longest range left to a request behind its prefix) / (longest context) at which the call still wins:
+# bf16 2688 / 4224 (1536 / 2560: 0.92; 3200 / 4224 does not win); fp8 2176 / 4224, and only with one length for all groups
+# (MAX_LEN_SPREAD_FP8: the smallest measured difference, 1024 tokens, loses).  A step with a long request in no group is
+# therefore REFUSED; one whose ungrouped requests are short against the longest context is taken.
+PREFIX_GROUPS_MIN_MEMBERS = 4
+PREFIX_GROUPS_MIN_MEMBERS_FP8 = 8
+PREFIX_GROUPS_MAX_SUFFIX_FRACTION = 0.64       # 2688 / 4224 = 0.636 wins, 3200 / 4224 = 0.758 does not
+PREFIX_GROUPS_MAX_SUFFIX_FRACTION_FP8 = 0.52   # 2176 / 4224 = 0.515, the one ratio measured to win
+PREFIX_GROUPS_MAX_LEN_SPREAD_FP8 = 31          # tokens between the longest and the shortest group prefix (one served length)
+
+
+def host_block_table(block_table):
+    """The step's block table as a host numpy array [requests, blocks], or None.  Accepts a numpy array (the stand-in's
+    `input_batch.block_table`), an object with `get_numpy_array()` or `block_table_np` (vLLM 0.9.2's BlockTable; names
+    recalled from 0.9.2, parity unpinned: DESIGN section 3), or a one-element sequence of such (its MultiGroupBlockTable
+    with one kv-cache group).  More than one kv-cache group, or anything else, is None: no groups."""
+    import numpy as np
+    for _ in range(2):
+        if isinstance(block_table, np.ndarray):
+            return block_table if block_table.ndim == 2 else None
+        get = getattr(block_table, "get_numpy_array", None)
+        if callable(get):
+            block_table = get()
+            continue
+        inner = getattr(block_table, "block_table_np", None)
+        if inner is not None:
+            block_table = inner
+            continue
+        tables = getattr(block_table, "block_tables", block_table)
+        if isinstance(tables, (list, tuple)) and len(tables) == 1:
+            block_table = tables[0]
+            continue
+        return None
+    return block_table if isinstance(block_table, np.ndarray) and block_table.ndim == 2 else None
+
+
+def prefix_groups(block_table_np, num_computed, q_lens, block_size, num_kv_heads, fp8):
+    """Which requests of a verify step read a shared prefix once, in groups (ops.PrefixGroups' `req_group` and
+    `group_prefix_len`), or None for the plain call: the whole decision, on host arrays alone.  Requests are bucketed by
+    their first SHARED_PREFIX_MIN_LEN // block_size block ids (prefix caching gives requests with the same leading tokens
+    the same pages); a bucket's shared length is its longest run of equal leading block-table columns times the block
+    size, capped by its members' smallest computed-token count (so that every query token lies behind it).  Kept: groups
+    of at least PREFIX_GROUPS_MIN_MEMBERS (_FP8) members and SHARED_PREFIX_MIN_LEN tokens (never fewer than 32), at most
+    PREFIX_GROUPS_MAX of them, largest first — the rest stay ungrouped — and only when the grouped requests x
+    `num_kv_heads` reach SHARED_PREFIX_MIN_ITEMS (_FP8), no request keeps more than PREFIX_GROUPS_MAX_SUFFIX_FRACTION
+    (_FP8) of the longest context behind its prefix (a request in no group keeps all of its own) and, with an fp8 cache,
+    the groups' served lengths are within PREFIX_GROUPS_MAX_LEN_SPREAD_FP8 of each other.  Correctness never depends on
+    the answer."""
+    import numpy as np
+    bt = host_block_table(block_table_np)
+    if bt is None or num_computed is None or q_lens is None or not block_size:
+        return None
+    B = len(q_lens)
+    block_size = int(block_size)
+    if B == 0 or bt.shape[0] < B or len(num_computed) < B:
+        return None
+    bt = bt[:B]
+    computed = np.asarray(num_computed)[:B].astype(np.int64)
+    min_len = max(SHARED_PREFIX_FLOOR, SHARED_PREFIX_MIN_LEN)
+    n_key = max(1, min_len // block_size)
+    if bt.shape[1] < n_key:
+        return None
+    min_members = max(1, PREFIX_GROUPS_MIN_MEMBERS_FP8 if fp8 else PREFIX_GROUPS_MIN_MEMBERS)
+    buckets = {}
+    for i in np.flatnonzero(computed >= min_len):
+        buckets.setdefault(bt[i, :n_key].tobytes(), []).append(int(i))
+    found = []
+    for members in buckets.values():
+        if len(members) < min_members:
+            continue
+        rows = bt[members]
+        differ = np.flatnonzero((rows != rows[0]).any(axis=0))
+        run = int(differ[0]) if differ.size else rows.shape[1]
+        length = min(run * block_size, int(computed[members].min()))
+        if length >= min_len:
+            found.append((members, length))
+    found.sort(key=lambda f: (-len(f[0]), f[0][0]))
+    found = found[:PREFIX_GROUPS_MAX]
+    grouped = sum(len(m) for m, _ in found)
+    if grouped * int(num_kv_heads or _MEASURED_KV_HEADS) < (SHARED_PREFIX_MIN_ITEMS_FP8 if fp8 else SHARED_PREFIX_MIN_ITEMS):
+        return None
+    if not found:
+        return None
+    req_group = np.full(B, -1, dtype=np.int32)
+    begin = np.zeros(B, dtype=np.int64)
+    for g, (members, length) in enumerate(found):
+        req_group[members] = g
+        begin[members] = length & ~31
+    # the measured limits of the win (above): the longest range any request keeps, and (fp8) one length for all groups
+    seq = computed + np.asarray(q_lens, dtype=np.int64)
+    fraction = PREFIX_GROUPS_MAX_SUFFIX_FRACTION_FP8 if fp8 else PREFIX_GROUPS_MAX_SUFFIX_FRACTION
+    if int((seq - begin).max()) > fraction * int(seq.max()):
+        return None
+    served = [length & ~31 for _, length in found]
+    if fp8 and max(served) - min(served) > PREFIX_GROUPS_MAX_LEN_SPREAD_FP8:
+        return None
+    return req_group, [length for _, length in found]
+

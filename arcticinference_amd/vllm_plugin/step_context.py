@@ -21,33 +21,48 @@ _q_lens: Optional[np.ndarray] = None
 _shift_mode: bool = False
 _prefill_on: bool = False
 _shared_prefix_on: bool = False
+_prefix_groups_on: bool = False
+_group_inputs = None                             # (host block table, computed tokens per request, block size) or None
+_groups: Dict[Tuple[int, bool, int], object] = {}   # (kv heads, fp8 cache, device index) -> ops.PrefixGroups | None
 _splits: Dict[Tuple[int, int], object] = {}     # (group size, device index) -> ops.split_requests(...) of this step
 _step_splits: Dict[Tuple[int, int], object] = {}  # (group size, device index) -> ops.StepSplit of this step
 # attention calls routed to the HIP kernels (verify: all of them; prefill: those of them with prefill chunks) / left to
 # vLLM's backend
 # shared_prefix: those of the verify calls that read a shared prompt prefix once (SHARED_PREFIX_ENV)
-calls = {"verify": 0, "fallback": 0, "prefill": 0, "shared_prefix": 0}
+# prefix_groups: those that read a prefix per group of requests once (PREFIX_GROUPS_ENV)
+calls = {"verify": 0, "fallback": 0, "prefill": 0, "shared_prefix": 0, "prefix_groups": 0}
 
 
 def prefill_switch() -> bool:
     return os.environ.get(PREFILL_ENV, "0").strip().lower() in ("1", "true", "yes", "on")
 
 
-def publish(num_scheduled_tokens: np.ndarray, shift_mode: bool) -> None:
-    global _q_lens, _shift_mode, _prefill_on, _shared_prefix_on
+def publish(num_scheduled_tokens: np.ndarray, shift_mode: bool, *, block_table=None, num_computed=None,
+            block_size: Optional[int] = None) -> None:
+    """`block_table` (the step's HOST block table, anything runner_logic.host_block_table reads), `num_computed` (tokens
+    already in the cache per request) and `block_size`: what the prefix-group detection needs; the runner passes them
+    only with PREFIX_GROUPS_ENV on.  Without them a step has no groups."""
+    global _q_lens, _shift_mode, _prefill_on, _shared_prefix_on, _prefix_groups_on, _group_inputs
     _q_lens = np.asarray(num_scheduled_tokens)
     _shift_mode = bool(shift_mode)
     _prefill_on = prefill_switch()
     _shared_prefix_on = shared_prefix_switch()
+    _prefix_groups_on = prefix_groups_switch()
+    _group_inputs = None
+    if _prefix_groups_on and block_table is not None and num_computed is not None and block_size:
+        _group_inputs = (block_table, num_computed, int(block_size))
     _splits.clear()
     _step_splits.clear()
+    _groups.clear()
 
 
 def clear() -> None:
-    global _q_lens
+    global _q_lens, _group_inputs
     _q_lens = None
+    _group_inputs = None
     _splits.clear()
     _step_splits.clear()
+    _groups.clear()
 
 
 def prefill_on() -> bool:
@@ -62,6 +77,30 @@ def shared_prefix_switch() -> bool:
 def shared_prefix_on() -> bool:
     """ARCTIC_INFERENCE_HIP_SHARED_PREFIX as read when the step was published (default off)."""
     return _shared_prefix_on
+
+
+def prefix_groups_switch() -> bool:
+    from .runner_logic import PREFIX_GROUPS_ENV
+    return os.environ.get(PREFIX_GROUPS_ENV, "0").strip().lower() in ("1", "true", "yes", "on")
+
+
+def prefix_groups_on() -> bool:
+    """ARCTIC_INFERENCE_HIP_PREFIX_GROUPS as read when the step was published (default off)."""
+    return _prefix_groups_on
+
+
+def prefix_groups(num_kv_heads: int, fp8: bool, device):
+    """ops.PrefixGroups of the published step for a layer with `num_kv_heads` local kv heads (built once per step and
+    shared by its layers), or None: switch off, nothing published for it, or runner_logic.prefix_groups said no."""
+    if not _prefix_groups_on or _group_inputs is None or _q_lens is None:
+        return None
+    key = (int(num_kv_heads), bool(fp8), device.index)
+    if key not in _groups:
+        from .. import ops
+        from .runner_logic import prefix_groups as decide
+        found = decide(_group_inputs[0], _group_inputs[1], _q_lens, _group_inputs[2], num_kv_heads, fp8)
+        _groups[key] = None if found is None else ops.PrefixGroups(found[0], found[1], _q_lens, device)
+    return _groups[key]
 
 
 def q_lens() -> Optional[np.ndarray]:

@@ -15,7 +15,8 @@ where this build differs from the reference on purpose: decode / verify steps (e
 MAX_SPEC_LEN + 1 query tokens) do not go to vLLM's attention backend but to aic_verify_attention_ex — and, with
 ARCTIC_INFERENCE_HIP_PREFILL=1, steps with prefill chunks go to aic_step_attention; with
 ARCTIC_INFERENCE_HIP_SHARED_PREFIX=1, steps vLLM marks for cascade attention read their common prefix once
-(aic_verify_attention_prefix) — and the copies around the all-to-alls are the fused HIP kernels of csrc/ulysses_pack.hip.
+(aic_verify_attention_prefix); with ARCTIC_INFERENCE_HIP_PREFIX_GROUPS=1, steps whose requests share prefixes in
+groups read each group's once (aic_verify_attention_prefix_groups) — and the copies around the all-to-alls are the fused HIP kernels of csrc/ulysses_pack.hip.
 """
 from __future__ import annotations
 
@@ -319,15 +320,29 @@ def build_ulysses_patches():
                     prefix, prefix_table = 0, None
                 elif not prefix_table.is_contiguous():         # a block table kept column-major or strided
                     prefix_table = prefix_table.contiguous()
+            # a step vLLM does not cascade (ARCTIC_INFERENCE_HIP_PREFIX_GROUPS): groups of requests with a prefix each,
+            # found on the host block table the runner published (runner_logic.prefix_groups is the whole decision).  The
+            # single-prefix path above keeps precedence; a windowed layer, capture, a step with prefill chunks (this is
+            # the "verify" route) and published lengths that do not describe this call are the plain call.
+            groups = None
+            if not prefix and not window and not capturing and step_context.prefix_groups_on():
+                ql = step_context.q_lens()
+                if (ql is not None and len(ql) == batch and int(ql.sum()) == n and meta.block_table.dtype == torch.int32
+                        and meta.block_table.is_contiguous()):
+                    groups = step_context.prefix_groups(self.num_kv_heads, fp8, query.device)
+                    if groups is not None and int(meta.max_seq_len) <= groups.max_prefix_len:
+                        groups = None
             ops.verify_attention(q, k_cache, v_cache, meta.block_table, meta.seq_lens.to(torch.int32),
                                  meta.query_start_loc.to(torch.int32), int(meta.max_query_len), int(meta.max_seq_len),
                                  float(self.impl.scale), out=out[:n].view(n, hq, D), req_split=split,
                                  k_scale=self._k_scale if fp8 else None, v_scale=self._v_scale if fp8 else None,
                                  sliding_window=window, sinks=sinks, shared_prefix_len=prefix,
-                                 prefix_block_table=prefix_table)
+                                 prefix_block_table=prefix_table, prefix_groups=groups)
             step_context.calls["verify"] += 1
             if prefix:
                 step_context.calls["shared_prefix"] += 1
+            if groups is not None:
+                step_context.calls["prefix_groups"] += 1
             return out
 
         def _arctic_sinks(self):

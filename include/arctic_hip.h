@@ -602,6 +602,51 @@ int aic_verify_attention_prefix(const void* q, int64_t q_stride, const void* k_c
                                 int max_seq_len, const int32_t* short_reqs, int n_short, const int32_t* long_reqs,
                                 int n_long, int sliding_window, const float* sinks, int q_dtype,
                                 int shared_prefix_len, const int32_t* prefix_block_table, void* stream);
+/* aic_verify_attention_dt for a step whose requests fall into GROUPS that each begin with the same tokens held in the same
+ * pages, beside requests that share nothing: agents with different system or tool prompts in one step, or one ad-hoc
+ * request among them.  vLLM's metadata of the step's one attention call (ulysses.py:510) says use_cascade only when EVERY
+ * request shares a prefix; this call serves the steps it does not mark.  The phases are those of
+ * aic_verify_attention_prefix, per group:
+ *   prefix phase: the rows of group g against keys [0, P_g), non-causal, through the block-table row of the group's leader
+ *                 (csrc/prefix_attn.hip, one launch for all groups, one split count for the call).  Every prefix slot of
+ *                 every row of the call is written by the call: rows of ungrouped requests and the slots a short group
+ *                 has no tiles for get the empty partial (max, sum) = (-inf, 0);
+ *   suffix phase: the bodies of aic_verify_attention_dt on keys [begin_i, seq_len_i) of each request, begin_i read on the
+ *                 device from req_prefix_len;
+ *   merge:        the combine launch over the partials of both.
+ *   n_groups: 0 .. aic_prefix_max_groups() (16).  0 is exactly aic_verify_attention_dt (the arrays may then be NULL).
+ *   group_prefix_len: HOST int32[n_groups], tokens the members of the group share, >= 0.  P_g = that rounded DOWN to a
+ *       multiple of 32; a group whose P_g is 0 is treated as ungrouped.
+ *   group_leader: HOST int32[n_groups], a member request in [0, batch): row group_leader[g] of block_table is the group's
+ *       prefix table.
+ *   group_token_start: HOST int32[n_groups + 1], non-decreasing, ending at or below num_tokens: the tokens of group g are
+ *       group_token_index[group_token_start[g] .. group_token_start[g + 1]).
+ *   group_token_index: DEVICE int32[group_token_start[n_groups]], token rows of the call (indices into q / out), sorted
+ *       by group.
+ *   req_prefix_len: DEVICE int32[batch], the prefix length of the request's group, 0 for a request in no group.  The
+ *       device rounds it down to a multiple of 32 as above and clamps it to the request's context.
+ * PRECONDITION (not checked here — lengths are device data; arcticinference_amd.ops checks it when it has host lengths):
+ *   for every member i of group g, seq_len_i - q_len_i >= group_prefix_len[g], its block-table columns below that length
+ *   are the leader's, its tokens are listed under g and req_prefix_len[i] = group_prefix_len[g].  A request that breaks it
+ *   gets rows that saw keys they should not, or an empty range; nothing is read out of bounds.
+ * Answered before any launch and before the device is looked for, AIC_ERR_INVALID: n_groups < 0 or above the cap, a NULL
+ * array with n_groups > 0, a negative length, a leader outside [0, batch), group_token_start decreasing or ending above
+ * num_tokens, max_seq_len <= the largest P_g.  sliding_window > 0 with n_groups > 0 is AIC_ERR_UNSUPPORTED; dtype and
+ * head-size rules are those of aic_verify_attention_dt.  Sinks, workspace, the library's side stream: as for
+ * aic_verify_attention_prefix.  Not for stream capture.  Not served: aic_step_attention*, aic_verify_attention_layers,
+ * nested prefixes (a group inside a group). */
+int aic_prefix_max_groups(void);
+int aic_verify_attention_prefix_groups(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache,
+                                       int64_t block_stride, int kv_dtype, const float* k_scale, const float* v_scale,
+                                       const int32_t* block_table, int max_blocks_per_seq, const int32_t* seq_lens,
+                                       const int32_t* query_start_loc, int batch, int num_tokens, int max_q_len,
+                                       int num_q_heads, int num_kv_heads, int head_size, int block_size, float sm_scale,
+                                       void* out, int64_t out_stride, void* workspace, size_t workspace_bytes,
+                                       int max_seq_len, const int32_t* short_reqs, int n_short, const int32_t* long_reqs,
+                                       int n_long, int sliding_window, const float* sinks, int q_dtype, int n_groups,
+                                       const int32_t* group_prefix_len /*host*/, const int32_t* group_leader /*host*/,
+                                       const int32_t* group_token_start /*host*/, const int32_t* group_token_index,
+                                       const int32_t* req_prefix_len, void* stream);
 /* aic_verify_attention_ex for `n_layers` layers of one engine step in one call: k_caches / v_caches are HOST arrays of
  * device pointers (one cache pair per layer, same shape / dtype / strides), q and out advance by *_layer_stride elements
  * per layer (0: shared).  For drivers that own the whole step (arcticinference_amd/engine.py); inside vLLM attention is

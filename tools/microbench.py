@@ -162,6 +162,85 @@ def attn_prefix(B=64, ctx=4224, P=2048, qlen=4, Hq=32, Hkv=8, D=128, bs=16, laye
           flush=True)
 
 
+def attn_prefix_groups(sizes, P, loners=0, ctx=4224, qlen=4, Hq=32, Hkv=8, D=128, bs=16, layers=4, kv8=False, rounds=5,
+                       iters=20, single=False):
+    """The same call plain and with its prefix groups (ops.verify_attention(..., prefix_groups=):
+    aic_verify_attention_prefix_groups against aic_verify_attention_dt), alternating in ONE process as attn_prefix does.
+    `sizes[g]` requests share their first `P[g]` tokens' pages (P: one length, or one per group), `loners` more share
+    nothing; members of the groups are interleaved in batch order.  `single`: with one group of everybody, the
+    single-prefix call (aic_verify_attention_prefix) takes part too.  Prints, per form, the median of `rounds` windows in
+    us per call (combine included) and the run's own max - min spread, and the ratios of the medians."""
+    lens = [P] * len(sizes) if isinstance(P, int) else list(P)
+    B = sum(sizes) + loners
+    req_group = []
+    left = list(sizes)
+    while any(left):                       # round-robin over the groups: A B C A B C ...
+        for g in range(len(sizes)):
+            if left[g]:
+                req_group.append(g)
+                left[g] -= 1
+    req_group += [-1] * loners
+    ql = [qlen] * B
+    nblk = (ctx + bs - 1) // bs
+    n_sh = [l // bs for l in lens]
+    nb = sum(n_sh) + sum(nblk - (n_sh[g] if g >= 0 else 0) for g in req_group)
+    perm = torch.randperm(nb, dtype=torch.int32)
+    bt = torch.empty(B, nblk, dtype=torch.int32)
+    k = 0
+    shared = []
+    for n in n_sh:
+        shared.append(perm[k:k + n])
+        k += n
+    for i, g in enumerate(req_group):
+        first = 0
+        if g >= 0:
+            first = n_sh[g]
+            bt[i, :first] = shared[g]
+        bt[i, first:] = perm[k:k + nblk - first]
+        k += nblk - first
+    bt = bt.to(dev)
+    seq = torch.full((B,), ctx, dtype=torch.int32, device=dev)
+    qsl = torch.tensor(np.concatenate([[0], np.cumsum(ql)]).astype(np.int32), device=dev)
+    rs = ops.split_requests(ql, Hq // Hkv, dev)
+    kw = {}
+    if kv8:
+        kvs = []
+        for _ in range(layers):
+            raw = torch.randint(0, 256, (2, nb, bs, Hkv, D), dtype=torch.uint8, device=dev)
+            raw[(raw & 0x7f) == 0x7f] = 0x30
+            kvs.append(raw.view(torch.float8_e4m3fn))
+        sc = torch.full((1,), 0.02, dtype=torch.float32, device=dev)
+        kw = dict(k_scale=sc, v_scale=sc)
+    else:
+        kvs = [torch.randn(2, nb, bs, Hkv, D, device=dev, dtype=torch.bfloat16) for _ in range(layers)]
+    q = torch.randn(sum(ql), Hq, D, device=dev, dtype=torch.bfloat16)
+    groups = ops.PrefixGroups(req_group, lens, ql, dev)       # once, as a step builds it for all its layers
+    extra = {"plain": {}, "groups": dict(prefix_groups=groups)}
+    if single:
+        assert len(sizes) == 1 and not loners
+        extra["prefix"] = dict(shared_prefix_len=lens[0], prefix_block_table=bt[0, :n_sh[0]].contiguous())
+    outs = {name: torch.empty_like(q) for name in extra}
+    fns = {}
+    for name in outs:
+        def f(name=name, i=[0]):
+            kv = kvs[i[0] % layers]
+            i[0] += 1
+            ops.verify_attention(q, kv[0], kv[1], bt, seq, qsl, qlen, ctx, D ** -0.5, out=outs[name], req_split=rs, **kw,
+                                 **extra[name])
+        fns[name] = f
+    times = {name: [] for name in fns}
+    for _ in range(rounds):
+        for name, f in fns.items():
+            times[name].append(timeit(f, iters=iters))
+    diff = max(float((outs["plain"].float() - outs[name].float()).abs().max()) for name in outs)
+    med = {name: float(np.median(t)) for name, t in times.items()}
+    shape = " + ".join(f"{n}x P={l}" for n, l in zip(sizes, lens)) + (f" + {loners} ungrouped" if loners else "")
+    print(f"prefixgroups{' fp8kv' if kv8 else ''} B={B} ({shape}) ctx={ctx} qlen={qlen} Hq={Hq} Hkv={Hkv}: " +
+          "  ".join(f"{name} med {med[name]:7.1f} spread {max(t) - min(t):5.1f} us" for name, t in times.items()) +
+          f"  groups / plain {med['groups'] / med['plain']:.3f}" +
+          (f"  groups / prefix {med['groups'] / med['prefix']:.3f}" if single else "") + f"  max |diff| {diff:.2g}", flush=True)
+
+
 def attn_mix(n_short=59, n_long=5, q_short=1, q_long=33, ctx=4224, Hq=32, Hkv=8, D=128, bs=16, layers=4, kv8=False):
     """The steady-state step of bench.py: most requests carry no draft (q_len 1), a few a long suffix draft — one call
     through the host-partitioned path (pair kernel) against its parts."""
@@ -820,6 +899,18 @@ if __name__ == "__main__":
         attn_prefix(B=64, P=2048, qlen=1)                # a step without drafts
         for B, P in ((8, 256), (16, 256), (8, 1024)):    # towards the break-even
             attn_prefix(B=B, P=P)
+    if "prefixgroups" in what:   # prefixes shared per GROUP of requests, read once per group, against the plain call
+        for kv8 in (False, True):
+            attn_prefix_groups([64], 2048, kv8=kv8, single=True)
+            for members in (32, 16, 8, 4):
+                attn_prefix_groups([members] * (64 // members), 2048, kv8=kv8)
+            attn_prefix_groups([24, 24], 2048, loners=16, kv8=kv8)
+            attn_prefix_groups([32, 32], [1024, 3072], kv8=kv8)
+            # what decides beside the group size: the longest range left to ONE request behind its prefix, against the
+            # longest context (the suffix launch lasts as long as its longest request)
+            attn_prefix_groups([32, 32], [2048, 3072], kv8=kv8)
+            attn_prefix_groups([32, 32], [1536, 2560], kv8=kv8)
+            attn_prefix_groups([31, 31], 2048, loners=2, kv8=kv8)
     if "prefixsplits" in what:   # split count of the prefix launch, forced (aic_debug_attn_prefix_splits)
         for kv8 in (False, True):
             for sp in (0, 1, 2, 4, 8, 16):
