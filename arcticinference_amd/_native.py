@@ -187,6 +187,17 @@ _SIGNATURES = {
                                                    c_size_t, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p,
                                                    c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                    c_void_p]),
+    # aic_verify_attention_dt's arguments without the request lists; sliding_window, shared_prefix_len (refused), sinks,
+    # q_dtype, tree_mask, stream
+    "aic_verify_attention_tree": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
+                                          c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                          c_int, c_float, c_void_p, c_int64, c_void_p, c_size_t, c_int, c_int, c_int,
+                                          c_void_p, c_int, c_void_p, c_void_p]),
+    "aic_rejection_tree_greedy": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                          c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p]),
+    "aic_kv_compact_paths": (c_int, [POINTER(c_void_p), POINTER(c_void_p), c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_void_p]),
     "aic_step_attention_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "aic_step_attention": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p,
                                    c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,

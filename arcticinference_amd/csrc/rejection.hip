@@ -1564,6 +1564,100 @@ static int dispatch_logprobs(const void* logits, int dtype, int64_t row_stride, 
   }
 }
 
+
+// ================================================================================================
+// Greedy acceptance over tree-shaped drafts (aic_rejection_tree_greedy).  The reference accepts paths only
+// (arctic_inference/vllm/model_runner.py:405-411 hands vLLM's RejectionSampler a chain); the rule over a tree is the
+// same walk with a choice of child: emit the arg-max of the current node's row, step to the child that carries it.
+// Phase 1 is the greedy row phase above, unchanged, over all T query rows (logits_row_kernel MODE 0: per-segment
+// (max, arg-max) partials, ties to the lowest index).  Phase 2 is one wavefront per request: lane t folds row t's
+// partials, learns through one shuffle whether node t carries its parent's arg-max, and the walk is a ballot + ffs per
+// level — wave-uniform, at most q_len - 1 levels.
+// ================================================================================================
+__global__ void __launch_bounds__(64)
+tree_accept_kernel(const float* __restrict__ part_val, const int32_t* __restrict__ part_idx, int n_splits,
+                   const int32_t* __restrict__ draft_ids, const int32_t* __restrict__ parent,
+                   const int32_t* __restrict__ qsl, int width, int32_t* __restrict__ out, int32_t* __restrict__ num_accepted,
+                   int32_t* __restrict__ last_token, int32_t* __restrict__ hidden_index, int32_t* __restrict__ path) {
+  const int req = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int start = qsl[req];
+  const int n = min(qsl[req + 1] - start, 64);   // one lane per node
+  int amax = -1, par = -1, tok = -1;
+  if (lane < n) {
+    const int row = start + lane;
+    Best b;
+    b.v = part_val[row * n_splits];
+    b.i = part_idx[row * n_splits];
+    for (int s = 1; s < n_splits; ++s) {
+      Best o;
+      o.v = part_val[row * n_splits + s];
+      o.i = part_idx[row * n_splits + s];
+      b = better(b, o);
+    }
+    amax = b.i;
+    if (lane > 0) {
+      par = parent[row];
+      tok = draft_ids[row];
+    }
+  }
+  // node t continues the walk from its parent iff it carries the parent's arg-max (a parent precedes its child)
+  const int par_amax = __shfl(amax, min(max(par, 0), 63));
+  const bool carries = lane > 0 && lane < n && par >= 0 && par < lane && tok == par_amax;
+  int cur = 0, depth = 0, my_tok = -1, my_node = -1, last = -1;
+  while (n > 0) {
+    const int a = __shfl(amax, cur);
+    if (lane == depth) {
+      my_tok = a;
+      my_node = cur;
+    }
+    last = a;
+    ++depth;
+    const unsigned long long next = __ballot(carries && par == cur);
+    if (!next) break;
+    cur = __ffsll(static_cast<long long>(next)) - 1;   // the lowest child that carries it (siblings carry distinct tokens)
+  }
+  if (lane < width) {
+    out[static_cast<int64_t>(req) * width + lane] = my_tok;
+    if (path) path[static_cast<int64_t>(req) * width + lane] = my_node;
+  }
+  if (lane == 0) {
+    if (num_accepted) num_accepted[req] = depth;
+    if (last_token) last_token[req] = last;
+    if (hidden_index) hidden_index[req] = start + cur;
+  }
+}
+
+template <typename T>
+static int run_rejection_tree(const void* logits, int64_t row_stride, int vocab, const int32_t* draft,
+                              const int32_t* parent, const int32_t* qsl, int batch, int rows, int max_q_len, int32_t* out,
+                              int32_t* nacc, int32_t* last, int32_t* hidx, int32_t* path, const int64_t* row_index,
+                              void* workspace, hipStream_t stream) {
+  const int S = pick_splits(rows, vocab);
+  int seg_len = (vocab + S - 1) / S;
+  seg_len = (seg_len + kSegQuantum - 1) / kSegQuantum * kSegQuantum;
+  const int n_splits = (vocab + seg_len - 1) / seg_len;
+  float* part_val = static_cast<float*>(workspace);
+  int32_t* part_idx = reinterpret_cast<int32_t*>(part_val + static_cast<size_t>(rows) * kMaxSplits);
+  const T* lg = static_cast<const T*>(logits);
+  const bool vec_ok = (reinterpret_cast<uintptr_t>(logits) % 16 == 0) && ((row_stride * sizeof(T)) % 16 == 0);
+  const dim3 grid(rows, n_splits);
+  // MODE 0 reads neither the draft ids, the request offsets nor the random-row state
+  if (vec_ok)
+    hipLaunchKernelGGL((logits_row_kernel<T, 0, true>), grid, dim3(256), 0, stream, lg, row_stride, vocab, seg_len, n_splits,
+                       nullptr, nullptr, batch, nullptr, nullptr, part_val, part_idx, nullptr, nullptr, nullptr, row_index,
+                       nullptr, rows);
+  else
+    hipLaunchKernelGGL((logits_row_kernel<T, 0, false>), grid, dim3(256), 0, stream, lg, row_stride, vocab, seg_len, n_splits,
+                       nullptr, nullptr, batch, nullptr, nullptr, part_val, part_idx, nullptr, nullptr, nullptr, row_index,
+                       nullptr, rows);
+  int rc = launch_status("logits_row_kernel");
+  if (rc != AIC_OK) return rc;
+  hipLaunchKernelGGL(tree_accept_kernel, dim3(batch), dim3(64), 0, stream, part_val, part_idx, n_splits, draft, parent, qsl,
+                     max_q_len, out, nacc, last, hidx, path);
+  return launch_status("tree_accept_kernel");
+}
+
 }  // namespace aic
 
 using namespace aic;
@@ -1585,6 +1679,38 @@ int aic_rejection_greedy(const void* target_logits, int logits_dtype, int64_t ro
   return dispatch(target_logits, logits_dtype, row_stride, vocab, draft_token_ids, cu_num_draft, bonus_token_ids,
                   nullptr, nullptr, nullptr, batch, num_draft_total, max_spec_len, out_token_ids, num_accepted,
                   last_token, hidden_index, target_row_index, bonus_row_index, workspace, stream, false);
+}
+
+int aic_rejection_tree_greedy(const void* target_logits, int logits_dtype, int64_t row_stride, int vocab,
+                              const int32_t* draft_token_ids, const int32_t* parent, const int32_t* query_start_loc,
+                              int batch, int num_tokens, int max_q_len, int32_t* out_token_ids, int32_t* num_accepted,
+                              int32_t* last_token, int32_t* hidden_index, int32_t* path, const int64_t* row_index,
+                              void* workspace, void* stream) {
+  if (batch == 0) return AIC_OK;
+  AIC_REQUIRE(target_logits && draft_token_ids && parent && query_start_loc && out_token_ids && workspace,
+              "null pointer argument to aic_rejection_tree_greedy");
+  AIC_REQUIRE(batch > 0 && num_tokens > 0 && vocab > 0, "non-positive size argument");
+  AIC_REQUIRE(max_q_len >= 1 && max_q_len <= 64, "max_q_len must be 1 .. 64 (one lane per node)");
+  if (logits_dtype != AIC_DT_F32 && logits_dtype != AIC_DT_BF16 && logits_dtype != AIC_DT_F16) {
+    set_error("unsupported logits dtype %d", logits_dtype);
+    return AIC_ERR_UNSUPPORTED;
+  }
+  AIC_NEED_DEVICE();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  switch (logits_dtype) {
+    case AIC_DT_F32:
+      return run_rejection_tree<float>(target_logits, row_stride, vocab, draft_token_ids, parent, query_start_loc, batch,
+                                       num_tokens, max_q_len, out_token_ids, num_accepted, last_token, hidden_index, path,
+                                       row_index, workspace, s);
+    case AIC_DT_BF16:
+      return run_rejection_tree<bf16_t>(target_logits, row_stride, vocab, draft_token_ids, parent, query_start_loc, batch,
+                                        num_tokens, max_q_len, out_token_ids, num_accepted, last_token, hidden_index, path,
+                                        row_index, workspace, s);
+    default:
+      return run_rejection_tree<f16_t>(target_logits, row_stride, vocab, draft_token_ids, parent, query_start_loc, batch,
+                                       num_tokens, max_q_len, out_token_ids, num_accepted, last_token, hidden_index, path,
+                                       row_index, workspace, s);
+  }
 }
 
 int aic_rejection_random(const void* target_logits, int logits_dtype, int64_t row_stride, int vocab,

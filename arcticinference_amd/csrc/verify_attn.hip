@@ -118,6 +118,23 @@ struct AttnParamsPfx : AttnParams {
   const int32_t* req_begin;
 };
 
+// What the TREE copies of the short body get (aic_verify_attention_tree), derived like AttnParamsPfx so that AttnParams
+// keeps its layout: tree_mask[t] (device uint64 per token row of the call) has bit u set iff query token u of the same
+// request is visible to token t — key base + u with base = ctx - q_len.  Keys below base are visible to every row.
+struct AttnParamsTree : AttnParams {
+  const uint64_t* tree_mask;
+};
+
+// The mask words a lane keeps for its rows: a member array in the TREE copies only.  (A plain local array, which the other
+// copies never read, still moved THEIR code: two-row-tile prologues rescheduled, a pair kernel's SGPR spills 28 -> 26;
+// with no such local the 138 kernels of the default path compile to the parent's instructions.  DESIGN.md section 4.)
+template <bool TREE, int MTQ>
+struct TreeMaskWords {};
+template <int MTQ>
+struct TreeMaskWords<true, MTQ> {
+  uint64_t w[MTQ];
+};
+
 template <bool PFX = false>
 __device__ __forceinline__ int window_begin(const AttnParams& P, int ctx, int q_len, int req) {
   if constexpr (PFX) {
@@ -162,11 +179,13 @@ constexpr float kLazySlack = 6.0f;   // long-draft body: a row's adopted maximum
 // exchange, no alpha and no rescale; l_part is this LANE's share of the row's sum (rowgroup_sum once, after the loop).
 // Masking is a real branch (the uniform need_mask test used to be if-converted: 16 selects, 22 compares and 24 scalar
 // ands on EVERY tile — ~60 of the fp8 body's ~380 instructions per tile, a loop SQ counters show issue-bound).
-template <int DT, typename E>
+// TREE (the copies aic_verify_attention_tree launches): `limit` is the request's base = ctx - q_len and `tmask` the row's
+// word of the tree mask; key tok is visible iff tok < base or bit tok - base of tmask is set (and tok < t_end as ever).
+template <int DT, typename E, bool TREE = false>
 __device__ __forceinline__ void softmax_tile(const f32x4& s0, const f32x4& s1, bool need_mask, bool row_ok, int tt,
                                              int g, int t_end, int limit, int wnd, float scale_log2, float inv_scale,
                                              float& m_run, float& l_part, f32x4 (&o)[DT], typename E::vec8& pf,
-                                             typename E::vec8& pl) {
+                                             typename E::vec8& pl, uint64_t tmask = 0) {
   float sc[8];
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
@@ -180,7 +199,13 @@ __device__ __forceinline__ void softmax_tile(const f32x4& s0, const f32x4& s1, b
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const int tok = tt + 16 * th + 4 * g + e;
-        if (!(row_ok && tok < t_end && tok <= limit && tok > limit - wnd)) sc[th * 4 + e] = -INFINITY;
+        if constexpr (TREE) {
+          // (tok < t_end <= ctx and q_len <= 64 keep the shift below 64; the & 63 only covers a caller that broke that)
+          const bool vis = tok < limit || ((tmask >> ((tok - limit) & 63)) & 1ull) != 0;
+          if (!(row_ok && tok < t_end && vis)) sc[th * 4 + e] = -INFINITY;
+        } else {
+          if (!(row_ok && tok < t_end && tok <= limit && tok > limit - wnd)) sc[th * 4 + e] = -INFINITY;
+        }
       }
   }
   const float lmax = max3f(max3f(max3f(sc[0], sc[1], sc[2]), sc[3], sc[4]), sc[5], max_nc(sc[6], sc[7]));
@@ -247,7 +272,8 @@ struct ShortLds {
 // one: K and V are fetched with the fp8 form's lane mapping (two 16-byte K loads per token group, four V loads per tile),
 // used as they are (no conversion), with two k-steps per score MFMA chain and four 16-wide output tiles.
 // E = the call's 16-bit element type (attn_common.h: ElemBf16 | ElemF16): what "bf16" stands for above in an f16 call.
-template <int MTQ, int HPW, bool KV8, int NW, int HD = kD, typename E = ElemBf16, bool PFX = false>
+// TREE: the copy aic_verify_attention_tree launches (verify_attn_tree_kernel); P is then the base of an AttnParamsTree.
+template <int MTQ, int HPW, bool KV8, int NW, int HD = kD, typename E = ElemBf16, bool PFX = false, bool TREE = false>
 __device__ __forceinline__ void verify_attn_body(const AttnParams& P, uint4* v_lds_raw, const int bx, const int by) {
   static_assert(HD == 128 || (HD == 64 && !KV8), "head size 128, or 64 with a 16-bit cache");
   using V8 = typename E::vec8;
@@ -350,6 +376,12 @@ __device__ __forceinline__ void verify_attn_body(const AttnParams& P, uint4* v_l
 #pragma unroll
     for (int s = 0; s < HD / 32; ++s)  // k-slot (s, g, j) -> d = 32 s + 8 g + j (bf16) | 64 (s/2) + 16 g + 8 (s%2) + j (fp8)
       qf[mt][s] = *reinterpret_cast<const uint4*>(qrow + (KV8 ? 64 * (s >> 1) + 16 * g + 8 * (s & 1) : 32 * s + 8 * g));
+  }
+
+  TreeMaskWords<TREE, MTQ> tmask;   // TREE: the tree-mask word of this lane's rows (no storage otherwise)
+  if constexpr (TREE) {
+#pragma unroll
+    for (int mt = 0; mt < MTQ; ++mt) tmask.w[mt] = static_cast<const AttnParamsTree&>(P).tree_mask[q0 + row_pos[mt]];
   }
 
   float m_run[MTQ], l_run[MTQ];
@@ -528,8 +560,15 @@ __device__ __forceinline__ void verify_attn_body(const AttnParams& P, uint4* v_l
       const bool need_mask = tn > t_end || tn > ctx - q_len + 1 || tt < ctx - wnd;
 #pragma unroll
       for (int mt = 0; mt < MTQ; ++mt) {
+        if constexpr (TREE) {
+          // the tile reaches the range end or the draft region [ctx - q_len, ctx), where the mask words decide
+          const bool tree_mask_tile = tn > t_end || tn > ctx - q_len;
+          softmax_tile<DT, E, true>(st[mt][0], st[mt][1], tree_mask_tile, row_ok[mt], tt, g, t_end, ctx - q_len, wnd, scale_log2,
+                                    inv_scale, m_run[mt], l_run[mt], o_acc[mt], pfrag[mt], pfrag_lo[mt], tmask.w[mt]);
+        } else {
         softmax_tile<DT, E>(st[mt][0], st[mt][1], need_mask, row_ok[mt], tt, g, t_end, ctx - q_len + row_pos[mt], wnd, scale_log2,
                          inv_scale, m_run[mt], l_run[mt], o_acc[mt], pfrag[mt], pfrag_lo[mt]);
+        }
       }
 
       // 4. O^T += V^T P^T : A = V^T fragment via transposing LDS reads
@@ -725,6 +764,14 @@ __global__ void __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((M
     verify_attn_body_dual<HPW, KV8, NW, HD, E, PFX>(P, v_lds_raw, blockIdx.x, blockIdx.y);
   else
     verify_attn_body<MTQ, HPW, KV8, NW, HD, E, PFX>(P, v_lds_raw, blockIdx.x, blockIdx.y);
+}
+
+// The generic form (MTQ = 1 | 2, row groups folded into the grid) with a tree mask: what aic_verify_attention_tree launches,
+// and nothing else does.  A kernel of its own so that verify_attn_kernel keeps its name, arguments and code.
+template <int MTQ, int HPW, bool KV8, int HD = kD, typename E = ElemBf16>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MTQ == 1 ? 3 : 2, MTQ == 1 ? 3 : 2))) verify_attn_tree_kernel(AttnParamsTree P) {
+  __shared__ uint4 v_lds_raw[ShortLds<MTQ, 4, HD>::kU4];
+  verify_attn_body<MTQ, HPW, KV8, 4, HD, E, false, true>(P, v_lds_raw, blockIdx.x, blockIdx.y);
 }
 
 // One 32-token KV tile (K and V images in LDS at kb / vb, v_tile_off layout) against the NT row tiles of a wave
@@ -2355,6 +2402,160 @@ int aic_verify_attention_prefix_groups(const void* q, int64_t q_stride, const vo
                                          num_q_heads, num_kv_heads, head_size, block_size, sm_scale, out, out_stride,
                                          workspace, workspace_bytes, max_seq_len, short_reqs, n_short, long_reqs, n_long,
                                          sliding_window, sinks, stream, 0, nullptr, &A, min_begin);
+}
+
+}  // extern "C"
+
+// ---- tree-shaped drafts (aic_verify_attention_tree) --------------------------------------------------------------------
+// One launch form: the generic one of the plain call without request lists — verify_attn_body with row groups folded into
+// the grid, the layout and split rules of that call — instantiated with the tree mask (verify_attn_tree_kernel), then the
+// ordinary combine launch.  A chain mask therefore takes, launch for launch, the arithmetic of
+// aic_verify_attention_dt(..., no lists): the two agree to the bit.  aic_debug_attn_layout's split count is honoured (tests
+// put a split boundary inside the draft region); its heads-per-workgroup value is not (the generic form has 4 and 1).
+template <typename E>
+static int verify_attention_tree_impl(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache,
+                                      int64_t block_stride, const bool kv8, const float* k_scale, const float* v_scale,
+                                      const int32_t* block_table, int max_blocks_per_seq, const int32_t* seq_lens,
+                                      const int32_t* query_start_loc, int batch, int num_tokens, int max_q_len,
+                                      int num_q_heads, int num_kv_heads, int head_size, int block_size, float sm_scale,
+                                      void* out, int64_t out_stride, void* workspace, size_t workspace_bytes,
+                                      int max_seq_len, const float* sinks, const uint64_t* tree_mask, void* stream) {
+  const bool d64 = head_size == 64;
+  const int G = num_q_heads / num_kv_heads;
+  const int max_rows = max_q_len * G;
+  const bool wave_heads = num_kv_heads % 4 == 0;
+  const int hpw = wave_heads ? 4 : 1;
+  const int hgroups = num_kv_heads / hpw;
+  const size_t rows = static_cast<size_t>(num_tokens) * num_q_heads;
+  int n_splits = pick_splits(batch * hgroups, max_seq_len, wave_heads ? 2 : 8, 1, 0);
+  if (g_force_splits) n_splits = std::min(g_force_splits, 64);
+  auto fits = [&](int parts) { return static_cast<size_t>(parts) * rows * (head_size + 2) * sizeof(float) <= workspace_bytes; };
+  while (n_splits > 1 && !fits(n_splits)) --n_splits;
+  AIC_REQUIRE(fits(n_splits), "workspace too small (%zu bytes)", workspace_bytes);
+
+  AttnParamsTree P;
+  P.q = static_cast<const uint16_t*>(q);
+  P.k_cache = static_cast<const uint16_t*>(k_cache);
+  P.v_cache = static_cast<const uint16_t*>(v_cache);
+  P.block_table = block_table;
+  P.seq_lens = seq_lens;
+  P.query_start_loc = query_start_loc;
+  P.ws_o = static_cast<float*>(workspace);
+  P.ws_ml = P.ws_o + static_cast<size_t>(n_splits) * rows * head_size;
+  P.q_stride = q_stride;
+  P.block_stride = block_stride;
+  P.max_blocks = max_blocks_per_seq;
+  P.num_q_heads = num_q_heads;
+  P.num_kv_heads = num_kv_heads;
+  P.block_size = block_size;
+  P.long_dma = g_long_dma;
+  P.bs_shift = (block_size & (block_size - 1)) == 0 ? __builtin_ctz(static_cast<unsigned>(block_size)) : -1;
+  P.n_splits = n_splits;
+  P.n_parts_total = n_splits;
+  P.total_rows = static_cast<int>(rows);
+  P.sm_scale = sm_scale;
+  P.req_list = nullptr;
+  P.k_scale = k_scale;
+  P.v_scale = v_scale;
+  P.dbg = 0;
+  P.trace = nullptr;
+  P.ptrace = nullptr;
+  P.ptrace_stride = 0;
+  P.out = static_cast<uint16_t*>(out);
+  P.out_stride = out_stride;
+  P.direct = 0;
+  P.mark_final = 0;
+  P.light_first = 0;
+  P.light_stride = 0;
+  P.light_pct = 100;
+  P.window = 0;
+  P.sinks = sinks;
+  P.tree_mask = tree_mask;
+  // the generic call's tile rule: one row tile per workgroup unless the common request has more than 24 rows
+  const int avg_rows = (num_tokens + batch - 1) / batch * G;
+  const int mtq = (max_rows <= 16 || avg_rows <= 24) ? 1 : 2;
+  P.m_groups = (max_rows + mtq * 16 - 1) / (mtq * 16);
+  P.n_items = batch * hgroups;
+  const dim3 grid(static_cast<unsigned>((P.n_items + 7) / 8 * 8 * P.m_groups), n_splits, 1);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+#define AIC_TREE_D(MTQ_, HPW_)                                                                  \
+  if (d64)                                                                                      \
+    launch(verify_attn_tree_kernel<MTQ_, HPW_, false, 64, E>, grid, dim3(256), s, P);           \
+  else if (kv8)                                                                                 \
+    launch(verify_attn_tree_kernel<MTQ_, HPW_, true, kD, E>, grid, dim3(256), s, P);            \
+  else                                                                                          \
+    launch(verify_attn_tree_kernel<MTQ_, HPW_, false, kD, E>, grid, dim3(256), s, P);
+  if (mtq == 1) {
+    if (hpw == 4) { AIC_TREE_D(1, 4) } else { AIC_TREE_D(1, 1) }
+  } else {
+    if (hpw == 4) { AIC_TREE_D(2, 4) } else { AIC_TREE_D(2, 1) }
+  }
+#undef AIC_TREE_D
+  int rc;
+  if ((rc = launch_ok("verify_attn_tree_kernel")) != AIC_OK) return rc;
+  if (d64)
+    launch(verify_attn_combine_kernel<64, E>, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), s, P.ws_o, P.ws_ml, n_splits,
+           static_cast<int>(rows), num_q_heads, static_cast<uint16_t*>(out), out_stride);
+  else
+    launch(verify_attn_combine_kernel<128, E>, dim3(static_cast<unsigned>((rows + 3) / 4)), dim3(256), s, P.ws_o, P.ws_ml, n_splits,
+           static_cast<int>(rows), num_q_heads, static_cast<uint16_t*>(out), out_stride);
+  return launch_ok("verify_attn_combine_kernel");
+}
+
+extern "C" {
+
+// Verify attention for tree-shaped drafts (include/arctic_hip.h).  The reference verifies paths only
+// (arctic_inference/vllm/model_runner.py:734-740: vLLM has no tree attention); its suffix trees already answer trees.
+int aic_verify_attention_tree(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache,
+                              int64_t block_stride, int kv_dtype, const float* k_scale, const float* v_scale,
+                              const int32_t* block_table, int max_blocks_per_seq, const int32_t* seq_lens,
+                              const int32_t* query_start_loc, int batch, int num_tokens, int max_q_len, int num_q_heads,
+                              int num_kv_heads, int head_size, int block_size, float sm_scale, void* out,
+                              int64_t out_stride, void* workspace, size_t workspace_bytes, int max_seq_len,
+                              int sliding_window, int shared_prefix_len, const float* sinks, int q_dtype,
+                              const uint64_t* tree_mask, void* stream) {
+  if (sliding_window != 0) {
+    set_error("tree-shaped drafts are not served on a layer with a sliding window");
+    return AIC_ERR_UNSUPPORTED;
+  }
+  if (shared_prefix_len != 0) {
+    set_error("tree-shaped drafts are not served together with a shared prefix");
+    return AIC_ERR_UNSUPPORTED;
+  }
+  if (batch == 0 || num_tokens == 0) return AIC_OK;
+  if (const int rc = attn_check_dtypes(q_dtype, kv_dtype); rc != AIC_OK) return rc;
+  const bool kv8 = kv_dtype == AIC_DT_FP8_E4M3;
+  AIC_REQUIRE(q && k_cache && v_cache && block_table && seq_lens && query_start_loc && out && workspace && tree_mask,
+              "null pointer argument to aic_verify_attention_tree");
+  AIC_REQUIRE(batch > 0 && num_tokens > 0 && max_q_len > 0 && num_q_heads > 0 && num_kv_heads > 0 && block_size > 0 &&
+                  max_blocks_per_seq > 0 && max_seq_len > 0,
+              "non-positive size argument");
+  AIC_REQUIRE(max_q_len <= 64, "max_q_len %d: a tree mask word covers 64 query tokens", max_q_len);
+  AIC_REQUIRE(num_q_heads % num_kv_heads == 0, "num_q_heads must be a multiple of num_kv_heads");
+  if (head_size != kD && head_size != 64) {
+    set_error("head_size %d not supported (128, or 64 with a 16-bit cache)", head_size);
+    return AIC_ERR_UNSUPPORTED;
+  }
+  if (head_size == 64 && kv8) {
+    set_error("head_size 64 needs a 16-bit kv cache");
+    return AIC_ERR_UNSUPPORTED;
+  }
+  AIC_REQUIRE(!kv8 || (k_scale && v_scale), "an fp8 kv cache needs k_scale and v_scale (device scalars)");
+  AIC_REQUIRE(q_stride % 8 == 0 && out_stride % 2 == 0 && block_stride % 16 == 0, "strides must keep 16-byte alignment");
+  if (block_size % 16 != 0) {
+    set_error("block_size %d not supported (must be a multiple of 16)", block_size);
+    return AIC_ERR_UNSUPPORTED;
+  }
+  AIC_NEED_DEVICE();
+  if (q_dtype == AIC_DT_F16)
+    return verify_attention_tree_impl<ElemF16>(q, q_stride, k_cache, v_cache, block_stride, kv8, k_scale, v_scale,
+                                               block_table, max_blocks_per_seq, seq_lens, query_start_loc, batch, num_tokens,
+                                               max_q_len, num_q_heads, num_kv_heads, head_size, block_size, sm_scale, out,
+                                               out_stride, workspace, workspace_bytes, max_seq_len, sinks, tree_mask, stream);
+  return verify_attention_tree_impl<ElemBf16>(q, q_stride, k_cache, v_cache, block_stride, kv8, k_scale, v_scale,
+                                              block_table, max_blocks_per_seq, seq_lens, query_start_loc, batch, num_tokens,
+                                              max_q_len, num_q_heads, num_kv_heads, head_size, block_size, sm_scale, out,
+                                              out_stride, workspace, workspace_bytes, max_seq_len, sinks, tree_mask, stream);
 }
 
 // ---- a run of layers as one graph launch ------------------------------------------------------------------------------

@@ -631,6 +631,170 @@ def split_requests(q_lens_host: Sequence[int], group_size: int, device, order_de
 
 
 # ------------------------------------------------------------------------------------------------
+# Tree-shaped drafts: tree-mask attention, greedy acceptance over the tree, KV compaction
+# ------------------------------------------------------------------------------------------------
+class TreeDrafts:
+    """The tree-shaped drafts of a step for verify_attention_tree / rejection_sample_tree / compact_accepted_paths:
+    per-request `(token_ids, parents)` in SuffixSpecResult form (tree_drafts.build_tree_layout checks and lays them out),
+    uploaded in one copy.  Build it once per step and hand it to every layer's call, like PrefixGroups.  Device tensors:
+    `tree_mask` (uint64 words as int64 [T]), `draft_token_ids` / `parents` int32 [T], `query_start_loc` int32 [B + 1];
+    `layout` keeps the host arrays (depths, q_lens: the model's rotary positions are tree_drafts.positions(layout, ...))."""
+
+    def __init__(self, trees: Sequence, device, root_tokens: Optional[Sequence[int]] = None):
+        import numpy as np
+
+        from . import tree_drafts as TD
+        lay = TD.build_tree_layout(trees, root_tokens)
+        self.layout = lay
+        self.batch, self.num_tokens = int(lay.q_lens.size), int(lay.tokens.size)
+        self.max_q_len = int(lay.q_lens.max()) if self.batch else 0
+        device = torch.device(device)
+        T, B = self.num_tokens, self.batch
+        # one buffer, the 8-byte mask words first: [masks as 2 T int32 | tokens T | parents T | query_start_loc B + 1]
+        host = torch.empty(4 * T + B + 1, dtype=torch.int32, pin_memory=device.type == "cuda")
+        hv = host.numpy()
+        hv[:2 * T] = lay.masks.view(np.int32)
+        hv[2 * T:3 * T] = lay.tokens
+        hv[3 * T:4 * T] = lay.parents
+        hv[4 * T:] = lay.query_start_loc
+        dev = host.to(device, non_blocking=True)
+        self._host, self._dev = host, dev
+        self.tree_mask = dev[:2 * T].view(torch.int64)
+        self.draft_token_ids, self.parents, self.query_start_loc = dev[2 * T:3 * T], dev[3 * T:4 * T], dev[4 * T:]
+
+
+def verify_attention_tree(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, block_table: torch.Tensor,
+                          seq_lens: torch.Tensor, tree: TreeDrafts, max_seq_len: int, sm_scale: float,
+                          out: Optional[torch.Tensor] = None, num_splits_max: int = 64,
+                          k_scale: Optional[torch.Tensor] = None, v_scale: Optional[torch.Tensor] = None,
+                          stream: Optional[int] = None, sinks: Optional[torch.Tensor] = None, sliding_window: int = 0,
+                          shared_prefix_len: int = 0) -> torch.Tensor:
+    """verify_attention for tree-shaped drafts (aic_verify_attention_tree): query token t of a request sees every key
+    below base = seq_len - q_len and the keys base + u of its ancestors-or-self u (`tree.tree_mask`).  Tensors, dtypes and
+    conventions as verify_attention; `seq_lens` counts the step's query tokens, whose K/V are already written at
+    base + t by the ordinary slot mapping.  `sliding_window` / `shared_prefix_len`: a layer's settings, forwarded so that a
+    non-zero value is refused (NativeError, AIC_ERR_UNSUPPORTED) rather than ignored."""
+    qd, kvd = _attn_dtypes(q, k_cache, v_cache, out)
+    T, Hq, D = q.shape
+    nb, bs, Hkv, D2 = k_cache.shape
+    if T != tree.num_tokens or seq_lens.numel() != tree.batch:
+        raise ValueError(f"the TreeDrafts describes {tree.batch} requests / {tree.num_tokens} tokens, the call has "
+                         f"{seq_lens.numel()} / {T}")
+    if sinks is not None and (sinks.dtype != torch.float32 or sinks.numel() != Hq or not sinks.is_contiguous()):
+        raise ValueError("sinks: contiguous float32, one value per query head")
+    assert D == D2 and q.stride(2) == 1 and q.stride(1) == D
+    refused = int(sliding_window or 0) != 0 or int(shared_prefix_len or 0) != 0
+    if not refused:
+        _need_cuda(q, k_cache, v_cache, block_table, seq_lens, tree.tree_mask, sinks)
+    if out is None:
+        out = torch.empty((T, Hq, D), dtype=q.dtype, device=q.device)
+    ws = None
+    if not refused:
+        ws = _workspace(N.lib().aic_verify_attention_workspace_bytes(T, Hq, D, num_splits_max), q.device, stream)
+    N.check(N.lib().aic_verify_attention_tree(
+        q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(0), kvd, _ptr(k_scale),
+        _ptr(v_scale), block_table.data_ptr(), block_table.size(1), seq_lens.data_ptr(), tree.query_start_loc.data_ptr(),
+        tree.batch, T, max(1, tree.max_q_len), Hq, Hkv, D, bs, float(sm_scale), out.data_ptr(), out.stride(0), _ptr(ws),
+        0 if ws is None else ws.numel(), int(max_seq_len), int(sliding_window or 0), int(shared_prefix_len or 0),
+        _ptr(sinks), qd, tree.tree_mask.data_ptr(), 0 if refused else (N.current_stream_ptr() if stream is None else stream)))
+    return out
+
+
+class TreeRejectionResult(RejectionResult):
+    __slots__ = ("path",)
+
+    def __init__(self, output_token_ids, num_accepted, last_token, hidden_index, path):
+        super().__init__(output_token_ids, num_accepted, last_token, hidden_index)
+        self.path = path
+
+
+def rejection_sample_tree(target_logits: torch.Tensor, tree: TreeDrafts,
+                          row_index: Optional[torch.Tensor] = None) -> TreeRejectionResult:
+    """Greedy acceptance over the step's trees (aic_rejection_tree_greedy).  `target_logits` [rows, V] with one row per
+    query token — row t of the step, or `target_logits[row_index[t]]` with `row_index` int64 [T] (the model's full
+    logits, un-gathered).  Per request: emit the arg-max of the current node's row, step to the child that carries it,
+    stop when none does.  Result: RejectionResult's fields (`output_token_ids` int32 [B, max_q_len], -1 padded) plus
+    `path` int32 [B, max_q_len], the nodes taken (path[:, 0] = 0, -1 behind the last).  Random acceptance over trees is
+    not served."""
+    if target_logits.dim() != 2 or target_logits.stride(1) != 1:
+        raise ValueError("target_logits must be [rows, V] with contiguous rows")
+    T, B = tree.num_tokens, tree.batch
+    if row_index is not None and (row_index.dtype != torch.int64 or row_index.numel() != T):
+        raise ValueError("row_index must be int64 with one entry per query token")
+    if row_index is None and target_logits.size(0) != T:
+        raise ValueError(f"target_logits has {target_logits.size(0)} rows, the step {T} query tokens")
+    _need_cuda(target_logits, tree.draft_token_ids, row_index)
+    dev = target_logits.device
+    W = max(1, tree.max_q_len)
+    V = int(target_logits.size(1))
+    out = torch.empty((B, W), dtype=torch.int32, device=dev)
+    path = torch.empty((B, W), dtype=torch.int32, device=dev)
+    nacc = torch.empty(B, dtype=torch.int32, device=dev)
+    last = torch.empty(B, dtype=torch.int32, device=dev)
+    hidx = torch.empty(B, dtype=torch.int32, device=dev)
+    if B == 0:
+        return TreeRejectionResult(out, nacc, last, hidx, path)
+    ws = _workspace(N.lib().aic_rejection_workspace_bytes(T, V), dev, purpose="accept")
+    N.check(N.lib().aic_rejection_tree_greedy(
+        target_logits.data_ptr(), N.torch_dtype_code(target_logits.dtype), int(target_logits.stride(0)), V,
+        tree.draft_token_ids.data_ptr(), tree.parents.data_ptr(), tree.query_start_loc.data_ptr(), B, T, W,
+        out.data_ptr(), nacc.data_ptr(), last.data_ptr(), hidx.data_ptr(), path.data_ptr(), _ptr(row_index), ws.data_ptr(),
+        N.current_stream_ptr()))
+    return TreeRejectionResult(out, nacc, last, hidx, path)
+
+
+class KvPathCompactor:
+    """compact_accepted_paths for a fixed set of caches: the checks and the per-layer pointer tables are done once (a
+    runner calls it every step with the same caches), as KvBulkWriter does for the KV write."""
+
+    def __init__(self, key_caches: List[torch.Tensor], value_caches: List[torch.Tensor]):
+        L = len(key_caches)
+        if L != len(value_caches):
+            raise RuntimeError("key_caches and value_caches must have the same length")
+        self.L = L
+        if L == 0:
+            return
+        _need_cuda(*key_caches, *value_caches)
+        kc0 = key_caches[0]
+        for c in list(key_caches) + list(value_caches):
+            if c.shape != kc0.shape or c.dtype != kc0.dtype or c.stride() != kc0.stride():
+                raise ValueError("every cache of the call must share shape, dtype and strides")
+        nb, bs, Hkv, D = kc0.shape
+        if kc0.stride(3) != 1 or kc0.stride(2) != D or kc0.stride(1) != Hkv * D:
+            raise ValueError("caches must be [num_blocks, block_size, Hkv, D] with contiguous pages")
+        VP = ctypes.c_void_p * L
+        self._keep = (list(key_caches), list(value_caches))   # the tables hold raw pointers
+        self.kc = VP(*[c.data_ptr() for c in key_caches])
+        self.vc = VP(*[c.data_ptr() for c in value_caches])
+        self.geom = (int(Hkv), int(D), int(kc0.element_size()), int(bs), int(kc0.stride(0)))
+
+    def __call__(self, block_table: torch.Tensor, seq_lens: torch.Tensor, tree: TreeDrafts, path: torch.Tensor,
+                 num_accepted: torch.Tensor, stream: Optional[int] = None) -> None:
+        if self.L == 0 or tree.batch == 0:
+            return
+        _need_cuda(block_table, seq_lens, path, num_accepted)
+        if path.dtype != torch.int32 or path.dim() != 2 or path.size(0) != tree.batch or not path.is_contiguous():
+            raise ValueError("path must be contiguous int32 [B, max_q_len]")
+        if num_accepted.dtype != torch.int32 or num_accepted.numel() != tree.batch:
+            raise ValueError("num_accepted must be int32 [B]")
+        N.check(N.lib().aic_kv_compact_paths(
+            self.kc, self.vc, self.L, block_table.data_ptr(), block_table.size(1), seq_lens.data_ptr(),
+            tree.query_start_loc.data_ptr(), path.data_ptr(), num_accepted.data_ptr(), tree.batch, int(path.size(1)),
+            *self.geom, N.current_stream_ptr() if stream is None else stream))
+
+
+def compact_accepted_paths(key_caches: List[torch.Tensor], value_caches: List[torch.Tensor], block_table: torch.Tensor,
+                           seq_lens: torch.Tensor, tree: TreeDrafts, path: torch.Tensor, num_accepted: torch.Tensor,
+                           stream: Optional[int] = None) -> None:
+    """After acceptance: node path[i][d]'s K and V move to key position seq_lens[i] - q_len_i + d in every layer's
+    caches, one launch (aic_kv_compact_paths).  `seq_lens` is the attention call's (query tokens counted); `path` /
+    `num_accepted` are rejection_sample_tree's.  Bytes are copied: any cache dtype.  Nothing outside the destination
+    slots changes; afterwards the cache is what decoding the accepted chain alone would have left.  A caller with a fixed
+    set of caches builds a KvPathCompactor once instead."""
+    KvPathCompactor(key_caches, value_caches)(block_table, seq_lens, tree, path, num_accepted, stream)
+
+
+# ------------------------------------------------------------------------------------------------
 # A5p whole-step attention: decodes, long drafts and prefill chunks in one call
 # ------------------------------------------------------------------------------------------------
 MAX_DECODE_Q_LEN = 33     # MAX_SPEC_LEN + 1: longer queries are prefill chunks (aic_step_attention's prefill body)

@@ -243,6 +243,23 @@ int aic_reshape_and_cache_flash_bulk(const void* keys, const void* values, void*
                                      const float* const* k_scale_ptrs /*host*/, const float* const* v_scale_ptrs /*host*/,
                                      void* stream);
 
+/* KV compaction after tree acceptance: node path[i][d]'s K and V move to key position base_i + d
+ * (base_i = seq_lens[i] - q_len_i, seq_lens counting the step's query tokens as in aic_verify_attention_tree), for
+ * d < num_accepted[i], in K and V of every layer, in one launch per 32 layers.  Afterwards the first num_accepted[i] slots
+ * behind base_i hold what decoding the accepted chain alone would have written.  Bytes are copied: elem_bytes (1, 2, 4)
+ * only sizes the token row (num_kv_heads * head_size * elem_bytes, a multiple of 16, as is the block stride in bytes:
+ * otherwise AIC_ERR_UNSUPPORTED).  key_cache_ptrs / value_cache_ptrs: HOST arrays of device pointers, passed to the kernel
+ * by value as in aic_reshape_and_cache_flash_bulk; block_stride in elements.  path int32 [B][max_q_len] and num_accepted
+ * int32 [B] are aic_rejection_tree_greedy's outputs (device); max_q_len <= 64.  Source and destination slots overlap: a
+ * unit of work reads all of its source rows before it writes any, so the result is the gather
+ * new[base + d] = old[base + path[d]].  Entries with path[d] == d, outside [0, q_len_i) or in a page the table lacks are
+ * left alone; nothing outside the destination slots changes.  Graph-capture safe. */
+int aic_kv_compact_paths(void* const* key_cache_ptrs /*host*/, void* const* value_cache_ptrs /*host*/, int num_layers,
+                         const int32_t* block_table, int max_blocks_per_seq, const int32_t* seq_lens,
+                         const int32_t* query_start_loc, const int32_t* path, const int32_t* num_accepted, int batch,
+                         int max_q_len, int num_kv_heads, int head_size, int elem_bytes, int block_size,
+                         int64_t block_stride, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * A6  Rejection acceptance — replaces the call into vllm.v1.sample.rejection_sampler
  *     (model_runner.py:405-411, parsed at :456-459) for draft_probs == None.
@@ -270,6 +287,23 @@ int aic_rejection_greedy(const void* target_logits, int logits_dtype, int64_t ro
                          int32_t* out_token_ids, int32_t* num_accepted, int32_t* last_token,
                          int32_t* hidden_index, const int64_t* target_row_index, const int64_t* bonus_row_index,
                          void* workspace, void* stream);
+/* Greedy acceptance over TREE-shaped drafts (the companion of aic_verify_attention_tree).  target_logits has one row per
+ * query token: row t of request i is target_logits[row_index[query_start_loc[i] + t]], or row query_start_loc[i] + t
+ * when row_index is NULL.  draft_token_ids int32 [num_tokens] (token 0's entry of a request is unused); parent int32
+ * [num_tokens], in-request indices: parent[0] = -1, parent[t] in [0, t - 1]; query_start_loc int32 [B + 1];
+ * q_len_i <= max_q_len <= 64.  Per request, cur = 0 and repeat: emit a = argmax(logits[row(cur)]) (ties to the lowest
+ * index, on the values as stored); step to the lowest c with parent[c] == cur and token[c] == a; stop when there is none.
+ * Outputs as aic_rejection_greedy's: out_token_ids int32 [B][max_q_len] (-1 padded) the emitted tokens, num_accepted their
+ * count, last_token the last one, hidden_index = query_start_loc[i] + (last node on the path); and path int32
+ * [B][max_q_len] (may be NULL), the node indices taken: path[0] = 0, -1 behind the last.  On chains (parent[t] = t - 1)
+ * every output equals aic_rejection_greedy's with bonus_row_index.
+ * Random (temperature) acceptance over trees is NOT served: it needs multi-draft rejection sampling, a different rule,
+ * not this walk with a coin.  workspace: >= aic_rejection_workspace_bytes(num_tokens, vocab). */
+int aic_rejection_tree_greedy(const void* target_logits, int logits_dtype, int64_t row_stride, int vocab,
+                              const int32_t* draft_token_ids, const int32_t* parent, const int32_t* query_start_loc,
+                              int batch, int num_tokens, int max_q_len, int32_t* out_token_ids, int32_t* num_accepted,
+                              int32_t* last_token, int32_t* hidden_index, int32_t* path, const int64_t* row_index,
+                              void* workspace, void* stream);
 /* Random rows (temperature > 0), draft_probs == None: accept draft iff softmax(logits/T)[draft] >= u,
  * else emit the recovered token argmax_v(p_v / q_v) with p[draft] := 0, q ~ Exp(1).
  * uniform: f64 [num_draft_total]; exp_noise: f32 [B][vocab]; temperature f32 [B]
@@ -647,6 +681,35 @@ int aic_verify_attention_prefix_groups(const void* q, int64_t q_stride, const vo
                                        const int32_t* group_prefix_len /*host*/, const int32_t* group_leader /*host*/,
                                        const int32_t* group_token_start /*host*/, const int32_t* group_token_index,
                                        const int32_t* req_prefix_len, void* stream);
+/* Verify attention for TREE-shaped drafts.  The reference verifies linear chains only (model_runner.py:734-740: vLLM has
+ * no tree attention) although its suffix trees answer trees (aic_sc_speculate_batch_tree); this call lifts that.
+ * A request has q_len = 1 + n query tokens: token 0 is the root (the last accepted token), tokens 1 .. n are draft nodes in
+ * the order the suffix tree emitted them, parent before child.  Node t's K/V are at key position base + t,
+ * base = seq_len - q_len: the ordinary slot mapping, no change to the KV write.  (Its rotary position is base + depth(t):
+ * the model's business.)
+ *   tree_mask: device uint64[num_tokens].  Bit u of token t's word: query token u of the same request is visible to t.
+ *       Every key below base is visible to every row; key base + u is visible to token t iff bit u is set; keys at or past
+ *       seq_len never.  The caller guarantees that bit t is set and no bit above t.  The lower-triangular mask
+ *       ((2 << t) - 1) is exactly the causal rule of aic_verify_attention_dt, and the call then computes, bit for bit, what
+ *       aic_verify_attention_dt without request lists computes.
+ *   Arguments otherwise as aic_verify_attention_dt, without request lists.  max_q_len <= 64 (one mask word; the suffix
+ *   proposer's trees have q_len <= 33).  Serves what the plain call serves: bf16 / f16 queries, a 16-bit cache of the
+ *   query's type or fp8 e4m3 at head size 128, a 16-bit cache at head size 64, any Hq / Hkv, sinks (a row's initial
+ *   state).  One launch form — the generic body with the mask test where the causal test is, in instantiations only this
+ *   call launches — and the ordinary combine launch; only tiles that overlap [base, seq_len) test the mask.
+ *   sliding_window and shared_prefix_len exist to be refused: a caller that forwards a layer's settings gets
+ *   AIC_ERR_UNSUPPORTED for any non-zero value, before any launch and before the device is looked for, instead of a mask
+ *   that silently means something else.  Not served either: aic_step_attention* (a step with prefill chunks),
+ *   aic_verify_attention_prefix*, aic_verify_attention_layers.
+ *   Workspace: aic_verify_attention_workspace_bytes, as for the plain call.  Graph-capture safe like aic_verify_attention. */
+int aic_verify_attention_tree(const void* q, int64_t q_stride, const void* k_cache, const void* v_cache,
+                              int64_t block_stride, int kv_dtype, const float* k_scale, const float* v_scale,
+                              const int32_t* block_table, int max_blocks_per_seq, const int32_t* seq_lens,
+                              const int32_t* query_start_loc, int batch, int num_tokens, int max_q_len,
+                              int num_q_heads, int num_kv_heads, int head_size, int block_size, float sm_scale,
+                              void* out, int64_t out_stride, void* workspace, size_t workspace_bytes,
+                              int max_seq_len, int sliding_window, int shared_prefix_len, const float* sinks,
+                              int q_dtype, const uint64_t* tree_mask, void* stream);
 /* aic_verify_attention_ex for `n_layers` layers of one engine step in one call: k_caches / v_caches are HOST arrays of
  * device pointers (one cache pair per layer, same shape / dtype / strides), q and out advance by *_layer_stride elements
  * per layer (0: shared).  For drivers that own the whole step (arcticinference_amd/engine.py); inside vLLM attention is

@@ -162,6 +162,122 @@ def attn_prefix(B=64, ctx=4224, P=2048, qlen=4, Hq=32, Hkv=8, D=128, bs=16, laye
           flush=True)
 
 
+def _alternate(fns, rounds, iters):
+    times = {name: [] for name in fns}
+    for _ in range(rounds):
+        for name, f in fns.items():
+            times[name].append(timeit(f, iters=iters))
+    return times, {name: float(np.median(t)) for name, t in times.items()}
+
+
+def _random_tree(n, rng, bushy=0.5):
+    """n draft nodes in SuffixSpecResult form (tokens distinct): a node hangs under the previous one or under any earlier."""
+    return ([int(x) for x in rng.permutation(30000)[:n]],
+            [c - 1 if rng.random() >= bushy else int(rng.integers(-1, c)) for c in range(n)])
+
+
+def attn_tree(B=64, n_draft=3, ctx=4224, Hq=32, Hkv=8, D=128, bs=16, layers=4, kv8=False, tree=False, rounds=5, iters=20):
+    """aic_verify_attention_tree against the plain call on the same step, alternating in ONE process: `lists` is the
+    plain call as the engine makes it (host query lengths: per-request tile choice, the long-draft body for long drafts),
+    `generic` the plain call without lists (the launch form the tree call shares), `chain` the tree call with
+    lower-triangular masks (computes what `generic` does, bit for bit), `tree` (with tree=True) the tree call on random
+    trees of n_draft nodes.  Prints each form's minimum / median / maximum and the ratios of the medians."""
+    rng = np.random.default_rng(n_draft + B)
+    q_len = n_draft + 1
+    ql = [q_len] * B
+    nblk = (ctx + bs - 1) // bs
+    nb = B * nblk
+    bt = torch.randperm(nb, device=dev).to(torch.int32).view(B, nblk)
+    seq = torch.full((B,), ctx, dtype=torch.int32, device=dev)
+    qsl = torch.tensor(np.concatenate([[0], np.cumsum(ql)]).astype(np.int32), device=dev)
+    rs = ops.split_requests(ql, Hq // Hkv, dev)
+    kw = {}
+    if kv8:
+        kvs = []
+        for _ in range(layers):
+            raw = torch.randint(0, 256, (2, nb, bs, Hkv, D), dtype=torch.uint8, device=dev)
+            raw[(raw & 0x7f) == 0x7f] = 0x30
+            kvs.append(raw.view(torch.float8_e4m3fn))
+        sc = torch.full((1,), 0.02, dtype=torch.float32, device=dev)
+        kw = dict(k_scale=sc, v_scale=sc)
+    else:
+        kvs = [torch.randn(2, nb, bs, Hkv, D, device=dev, dtype=torch.bfloat16) for _ in range(layers)]
+    q = torch.randn(sum(ql), Hq, D, device=dev, dtype=torch.bfloat16)
+    chain = ops.TreeDrafts([(list(range(n_draft)), list(range(-1, n_draft - 1)))] * B, dev)
+    forms = {"lists": None, "generic": None, "chain": chain}
+    if tree:
+        forms["tree"] = ops.TreeDrafts([_random_tree(n_draft, rng) for _ in range(B)], dev)
+    outs = {name: torch.empty_like(q) for name in forms}
+    fns = {}
+    for name, td in forms.items():
+        def f(name=name, td=td, i=[0]):
+            kv = kvs[i[0] % layers]
+            i[0] += 1
+            if td is None:
+                ops.verify_attention(q, kv[0], kv[1], bt, seq, qsl, q_len, ctx, D ** -0.5, out=outs[name],
+                                     req_split=rs if name == "lists" else None, **kw)
+            else:
+                ops.verify_attention_tree(q, kv[0], kv[1], bt, seq, td, ctx, D ** -0.5, out=outs[name], **kw)
+        fns[name] = f
+    times, med = _alternate(fns, rounds, iters)
+    same = bool(torch.equal(outs["generic"], outs["chain"]))
+    print(f"tree-attn{' fp8kv' if kv8 else ''} B={B} q_len={q_len} ctx={ctx} Hq={Hq} Hkv={Hkv}: " +
+          "  ".join(f"{name} min {min(t):7.1f} med {med[name]:7.1f} max {max(t):7.1f} us" for name, t in times.items()) +
+          f"  chain / generic {med['chain'] / med['generic']:.3f}  chain / lists {med['chain'] / med['lists']:.3f}" +
+          (f"  tree / chain {med['tree'] / med['chain']:.3f}" if tree else "") + f"  chain == generic: {same}", flush=True)
+
+
+def tree_accept_compact(B=64, n_draft=32, V=128256, layers=32, Hkv=8, D=128, bs=16, ctx=256, kv8=False, rounds=5, iters=20):
+    """The acceptance and compaction launches of a tree step: aic_rejection_tree_greedy over B trees of n_draft nodes
+    against aic_rejection_greedy over B chains of the same length (same logits, row_index forms), and aic_kv_compact_paths
+    over `layers` layers on the paths the acceptance took (logits planted so that every walk goes three levels deep through
+    a node's LAST child: rows move).  The caches are small (ctx tokens per request): the launch touches a few rows of each."""
+    rng = np.random.default_rng(B + n_draft)
+    trees = [_random_tree(n_draft, rng) for _ in range(B)]
+    td = ops.TreeDrafts(trees, dev)
+    lay = td.layout
+    T = td.num_tokens
+    logits = torch.randn(T, V, device=dev, dtype=torch.bfloat16)
+    for i in range(B):
+        q0, n, cur = int(lay.query_start_loc[i]), int(lay.q_lens[i]), 0
+        for _ in range(3):
+            kids = [c for c in range(1, n) if lay.parents[q0 + c] == cur]
+            if not kids:
+                break
+            logits[q0 + cur, int(lay.tokens[q0 + kids[-1]])] = 64.0
+            cur = kids[-1]
+    q_len = n_draft + 1
+    draft_rows = torch.tensor(np.concatenate([np.arange(i * q_len, i * q_len + n_draft) for i in range(B)]), device=dev)
+    bonus_rows = torch.tensor(np.arange(B) * q_len + n_draft, device=dev)
+    drafts = td.draft_token_ids.view(B, q_len)[:, 1:].reshape(-1).contiguous()
+    cu = torch.tensor(np.arange(1, B + 1) * n_draft, dtype=torch.int32, device=dev)
+    res = ops.rejection_sample_tree(logits, td)
+    fns = {"tree": lambda: ops.rejection_sample_tree(logits, td),
+           "chain": lambda: ops.rejection_sample(logits, drafts, cu, None, n_draft, target_row_index=draft_rows,
+                                                 bonus_row_index=bonus_rows)}
+    times, med = _alternate(fns, rounds, iters)
+    print(f"tree-accept B={B} n_draft={n_draft} V={V}: " +
+          "  ".join(f"{name} min {min(t):7.1f} med {med[name]:7.1f} max {max(t):7.1f} us" for name, t in times.items()) +
+          f"  tree / chain {med['tree'] / med['chain']:.3f}  mean accepted {float(res.num_accepted.float().mean()):.2f}", flush=True)
+    nblk = (ctx + bs - 1) // bs
+    nb = B * nblk
+    dt = torch.uint8 if kv8 else torch.bfloat16
+    kcs = [torch.zeros(nb, bs, Hkv, D, dtype=dt, device=dev) for _ in range(layers)]
+    vcs = [torch.zeros(nb, bs, Hkv, D, dtype=dt, device=dev) for _ in range(layers)]
+    bt = torch.randperm(nb, device=dev).to(torch.int32).view(B, nblk)
+    seq = torch.full((B,), ctx, dtype=torch.int32, device=dev)
+    moved = int(((res.path != torch.arange(res.path.size(1), device=dev)) & (res.path >= 0)).sum())
+    comp = ops.KvPathCompactor(kcs, vcs)                      # pointer tables built once, as a runner would
+    us = [timeit(lambda: comp(bt, seq, td, res.path, res.num_accepted), iters=iters) for _ in range(rounds)]
+    ident = torch.arange(res.path.size(1), dtype=torch.int32, device=dev).repeat(B, 1).contiguous()
+    us0 = [timeit(lambda: comp(bt, seq, td, ident, res.num_accepted), iters=iters) for _ in range(rounds)]
+    us1 = [timeit(lambda: ops.compact_accepted_paths(kcs, vcs, bt, seq, td, res.path, res.num_accepted), iters=iters)
+           for _ in range(rounds)]
+    print(f"tree-compact{' 1-byte' if kv8 else ''} B={B} layers={layers} Hkv={Hkv} D={D}: {moved} rows move per cache: min {min(us):7.1f} "
+          f"med {float(np.median(us)):7.1f} max {max(us):7.1f} us; identity paths (nothing moves) med {float(np.median(us0)):7.1f} us; "
+          f"through ops.compact_accepted_paths (tables rebuilt per call: host-bound) med {float(np.median(us1)):7.1f} us", flush=True)
+
+
 def attn_prefix_groups(sizes, P, loners=0, ctx=4224, qlen=4, Hq=32, Hkv=8, D=128, bs=16, layers=4, kv8=False, rounds=5,
                        iters=20, single=False):
     """The same call plain and with its prefix groups (ops.verify_attention(..., prefix_groups=):
@@ -899,6 +1015,17 @@ if __name__ == "__main__":
         attn_prefix(B=64, P=2048, qlen=1)                # a step without drafts
         for B, P in ((8, 256), (16, 256), (8, 1024)):    # towards the break-even
             attn_prefix(B=B, P=P)
+    if "tree" in what:       # tree-shaped drafts: the tree call against the plain call, acceptance and compaction launches
+        for kv8 in (False, True):
+            for n_draft in (3, 8):
+                attn_tree(B=64, n_draft=n_draft, kv8=kv8)
+        for kv8 in (False, True):
+            for n_draft in (16, 32):
+                attn_tree(B=16, n_draft=n_draft, kv8=kv8, tree=True)
+        attn_tree(B=64, n_draft=32, tree=True)
+        for n_draft in (8, 32):
+            tree_accept_compact(B=64, n_draft=n_draft)
+        tree_accept_compact(B=64, n_draft=32, kv8=True)
     if "prefixgroups" in what:   # prefixes shared per GROUP of requests, read once per group, against the plain call
         for kv8 in (False, True):
             attn_prefix_groups([64], 2048, kv8=kv8, single=True)
