@@ -311,7 +311,12 @@ def verify_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
 # bulk KV write (csrc/custom_ops/kernels.cu:29-68)
 # ----------------------------------------------------------------------------------------------
 def fp8_sat(x: torch.Tensor, kind: str) -> torch.Tensor:
-    """x (fp32) -> OCP fp8 with saturation to the largest finite value (CUDA __NV_SATFINITE)."""
+    """x (fp32) -> OCP fp8 with saturation to the largest finite value (CUDA __NV_SATFINITE): round to nearest even,
+    +-inf and everything beyond +-448 / +-57344 to the largest finite code, the sign of zero kept (bit for bit the
+    encoder of tests/fp8_codes.py on every bf16 and fp16 pattern, tests/test_fp8_codes_host.py).
+    NaN is where this restatement and the kernel part: torch keeps the sign (0x7f / 0xff), the bulk KV write
+    (csrc/kv_bulk_write.hip, f32_to_fp8_sat) answers EVERY NaN with 0x7f, sign and payload dropped, for e4m3 and e5m2
+    alike (tests/test_gpu_fp8_codes.py asserts it on the device).  Compare bytes outside NaN only."""
     if kind == "e4m3":
         return x.clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
     return x.clamp(-57344.0, 57344.0).to(torch.float8_e5m2)
