@@ -22,6 +22,22 @@ def _need_cuda(*ts: torch.Tensor) -> None:
             raise RuntimeError("arcticinference_amd ops run on the GPU only (got a CPU tensor); there is no CPU fallback")
 
 
+def _check_kv_layout(k_cache: torch.Tensor, v_cache: torch.Tensor) -> None:
+    """The cache layout every paged kernel assumes and none can check: [num_blocks, block_size, Hkv, D] with contiguous
+    pages (only the block stride is free: it is handed to the kernel), K and V alike.  A permuted view (an HND cache seen
+    as [nb, bs, Hkv, D]) would be read or written in the wrong places.  ValueError before anything is launched."""
+    if k_cache.dim() != 4:
+        raise ValueError(f"a kv cache is [num_blocks, block_size, Hkv, D], not {tuple(k_cache.shape)}")
+    nb, bs, Hkv, D = k_cache.shape
+    if k_cache.stride(3) != 1 or k_cache.stride(2) != D or k_cache.stride(1) != Hkv * D:
+        raise ValueError("caches must be [num_blocks, block_size, Hkv, D] with contiguous pages (strides "
+                         f"{tuple(k_cache.stride())} for shape {tuple(k_cache.shape)})")
+    if v_cache.shape != k_cache.shape or v_cache.dtype != k_cache.dtype or v_cache.stride() != k_cache.stride():
+        raise ValueError("key and value caches must share shape, dtype and strides "
+                         f"({tuple(k_cache.shape)} {k_cache.dtype} {tuple(k_cache.stride())} / "
+                         f"{tuple(v_cache.shape)} {v_cache.dtype} {tuple(v_cache.stride())})")
+
+
 # ------------------------------------------------------------------------------------------------
 # A16 bulk KV write — same signature as arctic_inference.py_custom_ops.reshape_and_cache_flash_bulk
 # (/root/reference/arctic_inference/py_custom_ops.py:40-54)
@@ -44,13 +60,15 @@ class KvBulkWriter:
         self.L = L
         if L == 0:
             return
+        for l, (kc, vc) in enumerate(zip(key_caches, value_caches)):   # every layer: one block stride serves the launch
+            _check_kv_layout(kc, vc)
+            if kc.shape != key_caches[0].shape or kc.dtype != key_caches[0].dtype or kc.stride() != key_caches[0].stride():
+                raise ValueError(f"layer {l}: every cache of the call must share shape, dtype and strides")
         _need_cuda(*key_caches, *value_caches)
         self.kvd = _KV_DTYPES[kv_cache_dtype]
         self.cache_dtype = key_caches[0].dtype
         self.block_size = int(key_caches[0].size(1))
         self.block_stride = int(key_caches[0].stride(0))
-        if self.block_stride != value_caches[0].stride(0):
-            raise RuntimeError("key and value caches must share the block stride")
         VP = ctypes.c_void_p * L
         self._keep = (list(key_caches), list(value_caches), list(k_scales), list(v_scales))   # the tables hold raw pointers
         self.kc = VP(*[c.data_ptr() for c in key_caches])
@@ -494,6 +512,7 @@ def verify_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     its group's length are its leader's), checked here when `seq_lens_host` or a CPU `seq_lens` is given.  Not together
     with `shared_prefix_len`, not with a sliding window.  None (the default) makes exactly the calls made without it."""
     qd, kvd = _attn_dtypes(q, k_cache, v_cache, out)
+    _check_kv_layout(k_cache, v_cache)
     shared_prefix_len = int(shared_prefix_len or 0)
     if prefix_groups is not None:
         if shared_prefix_len:
@@ -563,6 +582,7 @@ class VerifyAttentionPlan:
         if q.dtype != torch.bfloat16 or out.dtype != torch.bfloat16 or kv_like.dtype == torch.float16:
             raise ValueError("VerifyAttentionPlan serves bfloat16 queries and outputs with a bfloat16 or fp8 cache "
                              f"(got q {q.dtype}, out {out.dtype}, cache {kv_like.dtype}); fp16 models call verify_attention()")
+        _check_kv_layout(kv_like, kv_like)
         _need_cuda(q, out, kv_like, block_table, seq_lens, query_start_loc)
         T, Hq, D = q.shape
         nb, bs, Hkv, D2 = kv_like.shape
@@ -577,13 +597,18 @@ class VerifyAttentionPlan:
                       out.data_ptr(), out.stride(0), ws.data_ptr(), ws.numel(), int(max_seq_len),
                       _ptr(short) if n_short else None, n_short, _ptr(long_) if n_long else None, n_long,
                       N.current_stream_ptr() if stream is None else stream]
-        self._kv_shape, self._kv_dtype, self._kv_stride = tuple(kv_like.shape), kv_like.dtype, kv_like.stride(0)
+        self._kv_shape, self._kv_dtype, self._kv_stride = tuple(kv_like.shape), kv_like.dtype, tuple(kv_like.stride())
+
+    def _check_cache(self, c: torch.Tensor) -> None:
+        if tuple(c.shape) != self._kv_shape or c.dtype is not self._kv_dtype or tuple(c.stride()) != self._kv_stride:
+            raise ValueError("the plan was made for caches of another shape / dtype / strides")
 
     def layer_tables(self, k_caches: Sequence[torch.Tensor], v_caches: Sequence[torch.Tensor]):
         """Pointer tables for run_layers() (build once for a fixed set of caches)."""
+        if len(k_caches) != len(v_caches):
+            raise ValueError("k_caches and v_caches must have the same length")
         for c in list(k_caches) + list(v_caches):
-            if c.shape != self._kv_shape or c.dtype is not self._kv_dtype or c.stride(0) != self._kv_stride:
-                raise ValueError("the plan was made for caches of another shape / dtype")
+            self._check_cache(c)
         VP = ctypes.c_void_p * len(k_caches)
         return (VP(*[c.data_ptr() for c in k_caches]), VP(*[c.data_ptr() for c in v_caches]), len(k_caches),
                 (list(k_caches), list(v_caches)))
@@ -596,8 +621,8 @@ class VerifyAttentionPlan:
         N.check(N.lib().aic_verify_attention_layers(a[0], a[1], 0, kt, vt, n, *a[4:20], a[20], a[21], 0, *a[22:]))
 
     def run(self, k_cache: torch.Tensor, v_cache: torch.Tensor) -> None:
-        if k_cache.shape != self._kv_shape or k_cache.dtype is not self._kv_dtype or k_cache.stride(0) != self._kv_stride:
-            raise ValueError("the plan was made for caches of another shape / dtype")
+        self._check_cache(k_cache)
+        self._check_cache(v_cache)
         a = self._args
         a[2] = k_cache.data_ptr()
         a[3] = v_cache.data_ptr()
@@ -675,6 +700,7 @@ def verify_attention_tree(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch
     base + t by the ordinary slot mapping.  `sliding_window` / `shared_prefix_len`: a layer's settings, forwarded so that a
     non-zero value is refused (NativeError, AIC_ERR_UNSUPPORTED) rather than ignored."""
     qd, kvd = _attn_dtypes(q, k_cache, v_cache, out)
+    _check_kv_layout(k_cache, v_cache)
     T, Hq, D = q.shape
     nb, bs, Hkv, D2 = k_cache.shape
     if T != tree.num_tokens or seq_lens.numel() != tree.batch:
@@ -754,14 +780,13 @@ class KvPathCompactor:
         self.L = L
         if L == 0:
             return
-        _need_cuda(*key_caches, *value_caches)
         kc0 = key_caches[0]
         for c in list(key_caches) + list(value_caches):
             if c.shape != kc0.shape or c.dtype != kc0.dtype or c.stride() != kc0.stride():
                 raise ValueError("every cache of the call must share shape, dtype and strides")
+        _check_kv_layout(kc0, value_caches[0])
+        _need_cuda(*key_caches, *value_caches)
         nb, bs, Hkv, D = kc0.shape
-        if kc0.stride(3) != 1 or kc0.stride(2) != D or kc0.stride(1) != Hkv * D:
-            raise ValueError("caches must be [num_blocks, block_size, Hkv, D] with contiguous pages")
         VP = ctypes.c_void_p * L
         self._keep = (list(key_caches), list(value_caches))   # the tables hold raw pointers
         self.kc = VP(*[c.data_ptr() for c in key_caches])
@@ -862,6 +887,7 @@ def step_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor
     if sinks is not None and (sinks.dtype != torch.float32 or sinks.numel() != q.shape[1] or not sinks.is_contiguous()):
         raise ValueError("sinks: contiguous float32, one value per query head")
     qd, kvd = _attn_dtypes(q, k_cache, v_cache, out)
+    _check_kv_layout(k_cache, v_cache)
     _need_cuda(q, k_cache, v_cache, block_table, seq_lens, query_start_loc, sinks)
     T, Hq, D = q.shape
     nb, bs, Hkv, D2 = k_cache.shape
